@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — grid->displacements throughput of the MI355X path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--ppd P] [--plt 0|1] [--format RVZel] [--stream R]
+    python bench.py --gpus N --steps K --warmup W [--ppd P] [--plt 0|1] [--format RVZel] [--stream R] [--dump-outputs DIR]
 
 One "step" = one complete pass of the hot path over the workload: mode generation, Hermitian
 packing + z FFT, (all-to-all between ranks), y FFT, x FFT + particle epilogue for all ppd^3
@@ -165,6 +165,37 @@ def cpu_baseline(ppd, plt, fmt, eig):
                           time.time() - t0)}
 
 
+DUMP_SAMPLE = 1 << 20  # records in --dump-outputs: 24 - 60 MB as float32 / float64 arrays, whatever the record format
+DUMP_SEED = 12346
+
+
+def sample_records(ring, ppd, fmt):
+    """a fixed, seeded sample of the records in plane 0 of the record ring, as a numpy structured array of
+    zd.RECORD_DTYPES[fmt].  The last chunk of the last pass always starts at plane 0 of the ring, so after a step these are
+    records that step delivered; `ijk` (where the format has it) names the particle of each."""
+    import torch
+    import zeldovich_plt_amd.api as zd
+    dt = zd.RECORD_DTYPES[fmt]
+    n = ppd * ppd
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    plane = ring[:n * dt.itemsize].view(n, dt.itemsize)
+    rec = plane[torch.from_numpy(idx).to(ring.device)].cpu().numpy()
+    return np.ascontiguousarray(rec).view(dt).reshape(-1)
+
+
+def dump_outputs(outdir, rec):
+    """DIR/<field>.npy for every field of the sampled records but padding: d, v as stored (float32 / float64), ijk as
+    float32 (exact for lattice indices < 2^24)"""
+    os.makedirs(outdir, exist_ok=True)
+    for name in rec.dtype.names:
+        if name == "pad":
+            continue
+        a = rec[name]
+        if a.dtype.kind != "f":
+            a = a.astype(np.float32)
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def arm_last_words(make_line):
     """C-level handlers for SIGSEGV / SIGABRT / SIGBUS / SIGTERM that write make_line(signal) to stdout and end the process with
     status 128 + signal: the line survives, and the launcher still sees a failed rank (a faulted run must not read as rc = 0).
@@ -223,7 +254,12 @@ def main():
     ap.add_argument("--dist", action="store_true",
                     help="take the N > 1 code path (torch.distributed RCCL group, zd.Comm id broadcast, per-rank gathers) whatever "
                          "the world size: rehearses it on one GPU under torch.distributed.run --nproc-per-node 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of the particle records the last timed step delivered "
+                         "(rank 0) as DIR/<field>.npy (ijk, d, v)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # (dmabuf IPC: what RCCL between processes needs on this driver; normally exported already)
     import torch
@@ -283,9 +319,10 @@ def main():
             link["error"] = repr(e)
     choice_est = {}
 
-    def run_split(groups_req):
+    def run_split(groups_req, capture=False):
         """one measurement of the workload with the GPUs split into `groups_req` pass groups (0 = the library's choice): plan,
-        communicator, buffers, W warm-up + K timed steps between fences, per-rank spans.  The caller closes what it returns."""
+        communicator, buffers, W warm-up + K timed steps between fences, per-rank spans; capture: a sample of the records of the
+        last timed step (sample_records) before anything else uses the ring.  The caller closes what it returns."""
         # How the GPUs share the job (the library's policy, zd_choose_pass_groups): `groups` independent groups of gsz ranks;
         # group j runs the residue passes j, j + groups, ...; inside a group the rows / planes are sharded with one exchange per pass
         p.stream_factor = args.stream
@@ -342,6 +379,7 @@ def main():
         fence()
         dt = time.perf_counter() - t0
         st = plan.stats()
+        records = sample_records(pipe.ring, N, fmt) if capture else None
         per_rank = None
         if multi:
             t = torch.tensor([dt], dtype=torch.float64, device="cuda")
@@ -361,7 +399,7 @@ def main():
             if gsz > 1:  # ranks that exchange: RCCL must have been on the data path of EVERY rank
                 assert all(r["GB_sent_per_step"] > 0 for r in per_rank), per_rank
         return dict(groups=groups, R=R, gsz=gsz, grp_id=grp_id, plan=plan, comm=comm, pipe=pipe, pipelined=pipelined, dt=dt, st=st,
-                    per_rank=per_rank)
+                    per_rank=per_rank, records=records)
 
     def fence():
         torch.cuda.synchronize()
@@ -390,11 +428,14 @@ def main():
         torch.cuda.empty_cache()
 
     t_start = time.perf_counter()
-    main_mode = run_split(args.groups)
+    main_mode = run_split(args.groups, capture=bool(args.dump_outputs) and rank == 0)
     if main_mode is None:
         raise SystemExit("PPD=%d does not fit %d GPU(s)" % (N, world))
     groups, R, gsz, plan, comm, pipe, pipelined = (main_mode[k] for k in ("groups", "R", "gsz", "plan", "comm", "pipe", "pipelined"))
     dt, st, per_rank = main_mode["dt"], main_mode["st"], main_mode["per_rank"]
+    if main_mode["records"] is not None:
+        dump_outputs(args.dump_outputs, main_mode["records"])
+        main_mode["records"] = None
 
     # one extra UNTIMED pass with the two-stream overlap of the Z stage switched off: every kernel alone on the chip
     # (in the timed region k_gen and k_zfft share it, so their hipEvent spans there include each other)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/pcg_kat.json and tests/golden/spline_kat.json from the REFERENCE's own
+"""Generates tests/golden/pcg_kat.json, spline_kat.json, blockarray_kat.json and ref_object_kat.json from the REFERENCE's own
 object code (oracle/_ref/libzd_ref.so: include/pcg-rng/pcg_random.hpp and include/spline_function.h
 compiled where they lie under /root/reference).  Run in the build container only:
 
@@ -102,6 +102,45 @@ def main():
                          "slabs [zblock][zres][a][y][x] after all LoadBlock calls (pre-filled with `fill`)",
                "cases": cases}, open(os.path.join(HERE, "blockarray_kat.json"), "w"), indent=1)
     print("wrote blockarray_kat.json")
+
+    # The inputs of test_pcg_against_reference_object_code / test_blockarray_against_reference_object_code
+    # (tests/test_oracle_golden.py) with the reference's answers, so that those tests run where oracle/_ref is absent
+    json.dump({"source": "reference pcg64 and BlockArray object code via oracle/_ref, on the inputs of "
+                         "test_pcg_against_reference_object_code / test_blockarray_against_reference_object_code",
+               "pcg": pcg_trials(R), "blockarray": blockarray_cases(R)},
+              open(os.path.join(HERE, "ref_object_kat.json"), "w"), indent=1)
+    print("wrote ref_object_kat.json")
+
+
+def pcg_trials(R, n=50):
+    """seed -> state, advance by a random delta, five draws, distance back to the advanced state; numpy seed 3"""
+    rng = np.random.default_rng(3)
+    trials = []
+    for _ in range(n):
+        seed = int(rng.integers(0, 2 ** 63))
+        hi, lo = u64(), u64()
+        R.ref_pcg_seed(seed, C.byref(hi), C.byref(lo))
+        state0 = [hex(hi.value), hex(lo.value)]
+        delta = int(rng.integers(0, 2 ** 62)) << int(rng.integers(0, 40))
+        R.ref_pcg_advance(C.byref(hi), C.byref(lo), delta >> 64, delta & (2 ** 64 - 1))
+        a = (hi.value, lo.value)
+        out = (u64 * 5)()
+        R.ref_pcg_draw(C.byref(hi), C.byref(lo), 5, out)
+        trials.append({"seed": seed, "state0": state0, "delta": hex(delta), "after_advance": [hex(a[0]), hex(a[1])],
+                       "draws": [hex(int(x)) for x in out], "after_draws": [hex(hi.value), hex(lo.value)],
+                       "distance": int(R.ref_pcg_distance(a[0], a[1], hi.value, lo.value))})
+    return trials
+
+
+def blockarray_cases(R):
+    import hashlib
+    cases = []
+    for ppd, nb, na in [(8, 2, 2), (16, 4, 4), (24, 2, 2), (12, 6, 1)]:
+        arr, slabs = zdo.blockarray_roundtrip(R.ref_blockarray_roundtrip, ppd, nb, na)
+        cases.append({"ppd": ppd, "numblock": nb, "narray": na, "fill": -7.5,
+                      "arr_sha256": hashlib.sha256(arr.tobytes()).hexdigest(),
+                      "slabs_sha256": hashlib.sha256(slabs.tobytes()).hexdigest()})
+    return cases
 
 
 if __name__ == "__main__":

@@ -89,3 +89,18 @@ class NumpyEngine:
                     row = np.fft.ifft(buf[o:o + N]) * N
                     d = ((i * N + y) * self.na + a) * N  # out layout: [plane][y][a][x]
                     o_out[d:d + N] = row
+
+
+class CpuBarrierDist:
+    """torch.distributed as the CPU ranks of the gloo tests use it: barrier() is a one-element all_reduce on the CPU, everything
+    else is torch.distributed itself.  torch's own barrier() first asks for the machine's accelerator (torch._C._get_accelerator),
+    which initialises the GPU runtime in every rank on a GPU host; these ranks never use a GPU and must not open one."""
+
+    def __init__(self, dist):
+        self._dist = dist
+
+    def __getattr__(self, name):
+        return getattr(self._dist, name)
+
+    def barrier(self, group=None):
+        self._dist.all_reduce(torch.zeros(1), group=group)

@@ -2,7 +2,8 @@
   * against known-answer vectors generated from the reference's own pcg64 / SplineFunction object
     code (tests/golden/*.json, made by tests/golden/make_golden.py) and the vectors recorded from a
     reference run in SURVEY.md §8(c);
-  * live against oracle/_ref when that library exists (build container only);
+  * against the reference's answers on the inputs of the live comparisons (tests/golden/ref_object_kat.json), and live
+    against oracle/_ref as well where that library exists;
   * against an independent numpy formulation of the mode cube + FFT (SURVEY Appendix B1);
   * through the invariants the reference documents (README: NumBlock independence, oversampling,
     fix-to-mean phases) and its RNG-distance self check (src/zeldovich.cpp:478).
@@ -107,29 +108,40 @@ def test_spline_known_answers(oracle):
         assert np.max(np.abs(got - want) / np.maximum(np.abs(want), 1e-300)) < 1e-15
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLDEN), "..", "oracle", "_ref", "libzd_ref.so")),
-                    reason="oracle/_ref is only built where /root/reference is mounted")
 def test_pcg_against_reference_object_code(oracle):
-    R, L = oracle.ref(), oracle.lib()
-    rng = np.random.default_rng(3)
+    """the oracle's pcg64 against the reference's object code on 50 random seeds / advances: the reference's answers are
+    stored in tests/golden/ref_object_kat.json (made by tests/golden/make_golden.py); where oracle/_ref exists, the live
+    library must still give them"""
+    L = oracle.lib()
+    R = oracle.ref() if oracle.have_ref() else None
     u64 = C.c_uint64
-    for _ in range(50):
+    trials = json.load(open(os.path.join(GOLDEN, "ref_object_kat.json")))["pcg"]
+    assert len(trials) == 50
+    rng = np.random.default_rng(3)  # the inputs the vectors were recorded on
+    for t in trials:
         seed = int(rng.integers(0, 2 ** 63))
-        hi, lo = u64(), u64()
-        R.ref_pcg_seed(seed, C.byref(hi), C.byref(lo))
-        g = _pcg(oracle, seed)
-        assert (g.hi, g.lo) == (hi.value, lo.value)
         delta = int(rng.integers(0, 2 ** 62)) << int(rng.integers(0, 40))
-        R.ref_pcg_advance(C.byref(hi), C.byref(lo), delta >> 64, delta & M64)
+        assert (seed, hex(delta)) == (t["seed"], t["delta"])
+        g = _pcg(oracle, seed)
+        assert [hex(g.hi), hex(g.lo)] == t["state0"]
         L.zdo_pcg_advance(C.byref(g), delta >> 64, delta & M64)
-        assert (g.hi, g.lo) == (hi.value, lo.value)
-        out = (u64 * 5)()
-        a = (hi.value, lo.value)
-        R.ref_pcg_draw(C.byref(hi), C.byref(lo), 5, out)
-        assert [L.zdo_pcg_next(C.byref(g)) for _ in range(5)] == list(out)
+        assert [hex(g.hi), hex(g.lo)] == t["after_advance"]
+        a = (g.hi, g.lo)
+        assert [hex(L.zdo_pcg_next(C.byref(g))) for _ in range(5)] == t["draws"]
+        assert [hex(g.hi), hex(g.lo)] == t["after_draws"]
         # distance (the reference's operator-, used by its RNG self check)
         ga = oracle.Pcg(a[0], a[1])
-        assert L.zdo_pcg_distance(C.byref(ga), C.byref(g)) == R.ref_pcg_distance(a[0], a[1], hi.value, lo.value) == 5
+        assert L.zdo_pcg_distance(C.byref(ga), C.byref(g)) == t["distance"] == 5
+        if R is not None:
+            hi, lo = u64(), u64()
+            R.ref_pcg_seed(seed, C.byref(hi), C.byref(lo))
+            assert [hex(hi.value), hex(lo.value)] == t["state0"]
+            R.ref_pcg_advance(C.byref(hi), C.byref(lo), delta >> 64, delta & M64)
+            assert [hex(hi.value), hex(lo.value)] == t["after_advance"]
+            out = (u64 * 5)()
+            R.ref_pcg_draw(C.byref(hi), C.byref(lo), 5, out)
+            assert [hex(int(x)) for x in out] == t["draws"]
+            assert R.ref_pcg_distance(a[0], a[1], hi.value, lo.value) == t["distance"]
 
 
 # ---- independent formulation (numpy, SURVEY Appendix B1) -----------------------------------------
@@ -312,13 +324,18 @@ def test_blockarray_known_answers(oracle):
             assert np.array_equal(got[:, :, ys, :], inp[y].transpose(1, 0, 2))
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLDEN), "..", "oracle", "_ref", "libzd_ref.so")),
-                    reason="oracle/_ref only exists in the build container")
 def test_blockarray_against_reference_object_code(oracle):
-    for ppd, nb, na in [(8, 2, 2), (16, 4, 4), (24, 2, 2), (12, 6, 1)]:
-        a, b = oracle.blockarray_roundtrip(oracle.ref().ref_blockarray_roundtrip, ppd, nb, na)
-        c, d = oracle.blockarray_roundtrip(oracle.lib().zdo_blockarray_roundtrip, ppd, nb, na)
-        assert np.array_equal(a, c) and np.array_equal(b, d)
+    """StoreBlock / LoadBlock of the oracle against the reference's BlockArray object code, including non-power-of-two
+    sizes: images stored in tests/golden/ref_object_kat.json; where oracle/_ref exists, the live library must still give them"""
+    import hashlib
+    cases = json.load(open(os.path.join(GOLDEN, "ref_object_kat.json")))["blockarray"]
+    assert [(c["ppd"], c["numblock"], c["narray"]) for c in cases] == [(8, 2, 2), (16, 4, 4), (24, 2, 2), (12, 6, 1)]
+    fns = [oracle.lib().zdo_blockarray_roundtrip] + ([oracle.ref().ref_blockarray_roundtrip] if oracle.have_ref() else [])
+    for c in cases:
+        for fn in fns:
+            a, b = oracle.blockarray_roundtrip(fn, c["ppd"], c["numblock"], c["narray"], fill=c["fill"])
+            assert hashlib.sha256(a.tobytes()).hexdigest() == c["arr_sha256"], c
+            assert hashlib.sha256(b.tobytes()).hexdigest() == c["slabs_sha256"], c
 
 
 @pytest.mark.parametrize("plt,box", [(False, 720.0), (True, 720.0), (False, 3.0), (True, 6.0)])

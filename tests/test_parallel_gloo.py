@@ -29,7 +29,7 @@ def _worker(rank, world, port, n, R, outdir, group_bytes=None, groups=1):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from oracle import zdo
-    from standin_engine import NumpyEngine
+    from standin_engine import CpuBarrierDist, NumpyEngine
     from zeldovich_plt_amd.parallel import SlabPipeline, split_ranks
     pk = zdo.pk_from_file(WMAP, 720.0)
     cube = zdo.mode_cube(zdo.make_params(n, numblock=2), pk)
@@ -39,7 +39,8 @@ def _worker(rank, world, port, n, R, outdir, group_bytes=None, groups=1):
     pgs = [dist.new_group(list(range(j * gsz, (j + 1) * gsz))) for j in range(groups)] if groups > 1 else [None]
     eng = NumpyEngine(cube, n, R, grank, gsz)
     kw = dict(group_bytes=group_bytes) if group_bytes else {}
-    pipe = SlabPipeline(eng, n, world=gsz, dist=dist, device="cpu", chunk_bytes=3 * n * n * eng.record_size, rank_base=grp_id * gsz,
+    cdist = CpuBarrierDist(dist)  # (torch's barrier() would open the GPU in every rank on a GPU host)
+    pipe = SlabPipeline(eng, n, world=gsz, dist=cdist, device="cpu", chunk_bytes=3 * n * n * eng.record_size, rank_base=grp_id * gsz,
                         process_group=pgs[grp_id], **kw)
     if group_bytes:
         assert pipe.group_planes < eng.Zq  # several plane groups per pass: the pipelined form of the exchange
@@ -53,7 +54,7 @@ def _worker(rank, world, port, n, R, outdir, group_bytes=None, groups=1):
 
     pipe.run(consume, pass_first=grp_id, pass_step=groups)
     np.save(os.path.join(outdir, "rank%d.npy" % rank), got, allow_pickle=True)
-    dist.barrier()
+    cdist.barrier()
     dist.destroy_process_group()
 
 
