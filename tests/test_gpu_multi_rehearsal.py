@@ -163,6 +163,9 @@ def test_pipelined_passes_on_the_loopback_emulation(zd, oracle, ngpu, n, kw):
     dict(stream_factor=8),                                   # ZA field store: 4 passes of two residues
     dict(stream_factor=4, plt=True),                         # PLT: 4 passes
     dict(stream_factor=4, store_mode="reference"),           # reference arrays
+    dict(n=192, stream_factor=8),                            # composite ZA field store (z lines of 24): 4 passes of two residues
+    # the fused generator + z FFT of the packed PLT store: z lines of 512 at PPD = 1024, i.e. two passes (the most it takes)
+    dict(n=1024, stream_factor=2, plt=True, eig_ppd=128, fmt="ZelSimple", fused=True, min_passes=2),
 ])
 def test_one_rank_two_stores_equal_one_store(zd, oracle, kw):
     """ONE rank, zd_plan_run_passes with a second store (the branch behind `bench.py --two-stores`): the Z stage of pass p + 1 is
@@ -170,18 +173,20 @@ def test_one_rank_two_stores_equal_one_store(zd, oracle, kw):
     the one-store run of the same plan exactly (same kernels), and the records those of zd_generate."""
     import torch
     kw = dict(kw)
-    n, fmt = 256, kw.pop("fmt", "RVZel")
+    n, fmt = kw.pop("n", 256), kw.pop("fmt", "RVZel")
+    min_passes, fused = kw.pop("min_passes", 4), kw.pop("fused", False)
     ps = zd.PowerSpectrum.from_file(WMAP, 720.0)
     eig = None
+    eig_ppd = kw.pop("eig_ppd", 32)
     if kw.pop("plt", False):
-        eig = oracle.synthetic_eigenmodes(32)
+        eig = oracle.synthetic_eigenmodes(eig_ppd)
         kw.update(qPLT=1, qPLTrescale=1, PLT_target_z=5.0, z_initial=49.0)
     p = zd.make_params(n, icformat=fmt, **kw)
     dt = zd.RECORD_DTYPES[fmt]
 
     def run(two):
         plan = zd.Plan(p, ps, eig=eig)
-        assert plan.passes >= 4
+        assert plan.passes >= min_passes
         store = torch.empty(plan.exchange_bytes, dtype=torch.uint8, device="cuda")
         store2 = torch.empty_like(store) if two else None
         chunk = plan.plane_step * 3  # several record chunks per pass, the last one short
@@ -202,8 +207,10 @@ def test_one_rank_two_stores_equal_one_store(zd, oracle, kw):
         plan.close()
         return out, st
 
+    fused0 = sum(c for (nm, _l), c in zd.dispatch_report().items() if "launch_genz_t" in nm)
     a, sa = run(False)
     b, sb = run(True)
+    assert (sum(c for (nm, _l), c in zd.dispatch_report().items() if "launch_genz_t" in nm) > fused0) == fused
     assert sorted(a) == sorted(b) == list(range(n))
     for z in range(n):
         assert a[z].tobytes() == b[z].tobytes(), z

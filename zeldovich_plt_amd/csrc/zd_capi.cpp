@@ -1546,7 +1546,9 @@ static int stage_z_impl(zd_plan *pl, int residue, void *d_send, hipStream_t st, 
         if (detached && wait_ev) HIPCHECK(hipStreamWaitEvent(st, wait_ev, 0));
         B->pass_step = pl->pass_step;
         if (stage_z_impl(B, residue, d_send, st, false, nullptr, nullptr)) return 1;
+        pl->dens_pass = -1;
         if (zd_plan_stage_x_group(B, residue, d_send, B->Zq, 0, 0, (int64_t) B->Zq * 2, nullptr, pl->d_dens_pass, st)) return 1;
+        pl->dens_pass = residue;
         zd_plan *sub = pl->dens_sub;
         pl->dens_sub = nullptr;  // (the PLT pass itself)
         const int rc = stage_z_impl(pl, residue, d_send, st, false, nullptr, nullptr);
@@ -1623,7 +1625,9 @@ static int stage_z_impl(zd_plan *pl, int residue, void *d_send, hipStream_t st, 
         return 0;
     };
     const int accum = pl->g.accum_var;
-    if (pl->ahead_pass != residue) pl->ahead_n = 0;  // nothing (or something else) was started ahead
+    // nothing (or something else) was started ahead; or the variance is summed in this Z stage (the first after zd_plan_stats),
+    // which the slabs generated ahead — issued with accum = 0 — would leave out: they are generated again
+    if (pl->ahead_pass != residue || accum) pl->ahead_n = 0;
     for (int slab = 0; slab < nslab; slab++) {
         long long gno;
         if (slab < pl->ahead_n)
@@ -1711,6 +1715,11 @@ int zd_plan_stage_x_group(zd_plan *pl, int residue, const void *d_recv, int chun
         return 1;
     }
     if (d_density && pl->dens_sub) {  // the planes the density-only half left behind at the head of this pass's Z stage
+        if (pl->dens_pass != residue) {  // one buffer: a later Z stage has overwritten them (or no Z stage of this pass ran)
+            fprintf(stderr, "zeldovich_hip: stage_x density of pass %d requested, but the last Z stage was pass %d: only that pass can "
+                            "deliver density planes on this plan\n", residue, pl->dens_pass);
+            return 1;
+        }
         HIPCHECK(hipMemcpyAsync(d_density, pl->d_dens_pass + (size_t) gplane0 * pl->N * pl->N, (size_t) nplanes * pl->N * pl->N * sizeof(float),
                                 hipMemcpyDeviceToDevice, st));
         d_density = nullptr;

@@ -38,6 +38,7 @@ struct zd_plan {
     // the same store; they wait here, in delivery order, for the x stage's calls
     zd_plan *dens_sub = nullptr;
     float *d_dens_pass = nullptr;
+    int dens_pass = -1;  // the pass whose density planes d_dens_pass holds (the latest Z stage's; -1: none yet)
     int ring_planes = 0;
     int64_t store_bytes_ = 0;       // bytes of the send (= receive) buffer per pass
     // device tables
