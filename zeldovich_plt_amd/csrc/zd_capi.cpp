@@ -416,6 +416,26 @@ static bool np2_stream_factor_ok(int64_t N, int R) {
     return R >= 1 && (R == 1 || R % 2 == 0) && N % R == 0 && zd::np2_supported_zlen((int) (N / R));
 }
 
+// ZD_f_NL on a composite grid, one rank: the reference's arrays as on the convolution path (the second pass keeps the Nyquist
+// modes live, so the Hermitian field stores cannot carry it), every line through the composite transforms of
+// zd_kernels_np2_ref.hip where both line lengths — N (x, y; the phi round's z) and N / R (the z lines of a pass) — have one.
+// ZD_StoreMode = reference and ZD_qoneslab keep the convolution transforms, as does any stream factor outside fnl_np2_factor_ok.
+static bool fnl_np2(const zd_params *p, int nranks) {
+    return p->f_NL != 0. && nranks == 1 && !is_pow2(p->ppd) && zd::np2_supported_ppd((int) p->ppd) && p->store_mode != ZD_STORE_REFERENCE
+           && p->qoneslab < 0 && !tune_env("ZD_NO_NP2_FNL");
+}
+static bool fnl_np2_factor_ok(int64_t N, int R) {
+    return R >= 1 && N % R == 0 && zd::refq_supported_len((int) N) && zd::refq_supported_len((int) (N / R));
+}
+
+// ZD_f_NL memory: PhiK (half-space rows, [ky][kz][x]) and the phi round's planes — half-space rows on the composite transforms
+// (make_phik), the full store on the convolution ones
+static int64_t fnl_phik_bytes(int64_t N) { return (N / 2) * N * N * 16; }
+static int64_t fnl_phi_bytes(const zd_params *p, int nranks) {
+    const int64_t N = p->ppd;
+    return (fnl_np2(p, nranks) && fnl_np2_factor_ok(N, 1) ? N / 2 : N) * N * (N + store_row_pad(N)) * 16;
+}
+
 // ZD_qdensity = 2 (density only): the displacement arrays are never built (src/zeldovich.cpp:303,440), so the eigenmodes of ZD_qPLT
 // never enter — the run IS the ZA density-only run, on every grid and path
 static zd_params canonical(const zd_params *p) {
@@ -481,8 +501,17 @@ static int choose_stream_factor_one(const zd_params *p, int nranks, int64_t budg
     auto any_factor = [&]() -> int {
         if (N % 2 || N < 8 || N > 8192 || nranks != 1) return -1;
         const int64_t narray = p->qdensity == 2 ? 1 : (p->qPLT ? 4 : 2);
-        for (int R = 1; N / R >= 3; R++)  // any divisor of N (the z-residue fold is a plain decimation: R need not be 2^k here)
-            if (N % R == 0 && (N / R) * narray * N * (N + store_row_pad(N)) * 16 <= budget_bytes) return R;
+        int64_t budget = budget_bytes;
+        if (p->f_NL != 0.) {  // PhiK stays beside every pass's store; the phi round before it holds PhiK and the phi planes
+            const int64_t phik = fnl_phik_bytes(N);
+            if (fnl_phi_bytes(p, nranks) + phik > budget) return -1;
+            budget -= phik;
+        }
+        // f_NL on a composite grid: the smallest factor whose z lines the composite transforms take (fnl_np2) comes first
+        for (int pass = fnl_np2(p, nranks) ? 0 : 1; pass < 2; pass++)
+            for (int R = 1; N / R >= 3; R++)  // any divisor of N (the z-residue fold is a plain decimation: R need not be 2^k here)
+                if (N % R == 0 && (pass == 1 || fnl_np2_factor_ok(N, R)) && (N / R) * narray * N * (N + store_row_pad(N)) * 16 <= budget)
+                    return R;
         return -1;
     };
     if (np2 && (!zd::pack_is_fields(pack_mode(p, 2)) || !zd::np2_supported_ppd((int) N) || (N / 2) % (nranks * zd::FIELD_RB))) return any_factor();
@@ -645,6 +674,20 @@ int zd_choose_pass_groups_measured(const zd_params *p_in, int ngpu, int64_t budg
     return 0;
 }
 
+// the line transforms of the reference-array store (pl->any): composite (zd_kernels_np2_ref.hip) where the plan uploaded their
+// twiddles, else convolutions (zd_kernels_any.hip).  zlen: lines of length L (the z lines of a pass), else N.
+static int any_cols(const zd_plan *pl, bool zlen, void *data, long long batch_stride, long long point_stride, int ncols, int nbatch,
+                    int zero_point, hipStream_t st) {
+    if (pl->d_twr_n)
+        return zd::launch_refq_cols(zlen ? pl->L : pl->N, zlen ? pl->d_twr_l : pl->d_twr_n, data, batch_stride, point_stride, ncols, nbatch,
+                                    zero_point, st);
+    return zd::launch_any_cols(zlen ? pl->tabL : pl->tabN, data, batch_stride, point_stride, ncols, nbatch, zero_point, st);
+}
+static int any_lines(const zd_plan *pl, void *data, long long pitch, long long nlines, hipStream_t st) {
+    if (pl->d_twr_n) return zd::launch_refq_lines(pl->N, pl->d_twr_n, data, pitch, nlines, st);
+    return zd::launch_any_lines(pl->tabN, data, pitch, nlines, st);
+}
+
 // phi_mode 1: first f_NL pass (one array holding phi = D/M); phik != NULL: second pass (D = phik * M)
 static int plan_create_ex(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
                           int phi_mode, const cplx *phik, zd_plan **out);
@@ -662,23 +705,39 @@ static int make_phik(const zd_params *p, const zd_pk *pk, cplx **d_phik) {
     void *d_phi = nullptr;
     int frc     = 1;
     *d_phik     = nullptr;
+    // composite transforms (fnl_np2): phi is a real field, so the planes keep the half-space rows ky < N/2 only (k_refq_yphi rebuilds
+    // a column from its half) — 8 N^3 bytes beside PhiK's 8 N^3 where the full store held 16 N^3
+    ph->phi_half = ph->d_twr_n != nullptr && ph->jobs.n == 1 && ph->R == 1;
+    const int64_t phi_bytes = ph->phi_half ? (N / 2) * N * ph->AL.pitch * 16 : zd_plan_exchange_bytes(ph);
     do {
-        if (zd_store_alloc(&d_phi, (size_t) zd_plan_exchange_bytes(ph)) != hipSuccess
+        if (zd_store_alloc(&d_phi, (size_t) phi_bytes) != hipSuccess
             || zd_store_alloc((void **) d_phik, (size_t) (N / 2) * N * N * 16) != hipSuccess) {
             fprintf(stderr, "zeldovich_hip: f_NL needs %.1f GB of HBM for the phi field at PPD %lld\n",
-                    (zd_plan_exchange_bytes(ph) + (N / 2) * N * N * 16) / 1e9, (long long) N);
+                    (phi_bytes + (N / 2) * N * N * 16) / 1e9, (long long) N);
             break;
         }
         fprintf(stderr, "Generating phi field\n");
-        if (zd_plan_stage_z(ph, 0, d_phi, 0) || zd_plan_stage_y(ph, d_phi, 0)) break;
-        if (ph->any) {  // convolution-transform PPDs: x inverse, phi + f_NL phi^2, then the forward 3-D transform of that REAL
-                        // field as the conjugate of its inverse transform (x, y, z in place; conjugated while PhiK is laid out)
+        if (zd_plan_stage_z(ph, 0, d_phi, 0)) break;
+        if (ph->phi_half) {  // x inverse, y inverse + phi + f_NL phi^2 + y, x, then z into PhiK (conjugated: see below)
+            const long long pitch = ph->AL.pitch, plane = (long long) (N / 2) * pitch;
+            if (any_lines(ph, d_phi, pitch, (long long) N * (N / 2), 0)) break;
+            if (zd::launch_refq_yphi((int) N, ph->d_twr_n, d_phi, pitch, (int) N, p->f_NL, 0)) break;
+            if (any_lines(ph, d_phi, pitch, (long long) N * (N / 2), 0)) break;
+            if (zd::launch_refq_cols_oop((int) N, ph->d_twr_n, d_phi, pitch, plane, *d_phik, N * N, N, (int) N, (int) (N / 2), true, 0)) break;
+            if (hipDeviceSynchronize() != hipSuccess) break;
+            frc = 0;
+            break;
+        }
+        if (zd_plan_stage_y(ph, d_phi, 0)) break;
+        if (ph->any) {  // reference-array PPDs: x inverse, phi + f_NL phi^2, then the forward 3-D transform of that REAL field as the
+                        // conjugate of its inverse transform (x, y, z in place; conjugated while PhiK is laid out).  The lines go
+                        // through the composite transforms on the composite grids (fnl_np2), else as convolutions.
             const long long plane = (long long) N * ph->AL.pitch;
-            if (zd::launch_any_lines(ph->tabN, d_phi, ph->AL.pitch, (long long) N * N, 0)) break;
+            if (any_lines(ph, d_phi, ph->AL.pitch, (long long) N * N, 0)) break;
             if (zd::launch_any_phi_nl(ph->AL, p->f_NL, d_phi, 0)) break;
-            if (zd::launch_any_lines(ph->tabN, d_phi, ph->AL.pitch, (long long) N * N, 0)) break;
-            if (zd::launch_any_cols(ph->tabN, d_phi, plane, ph->AL.pitch, (int) N, (int) N, -1, 0)) break;
-            if (zd::launch_any_cols(ph->tabN, d_phi, ph->AL.pitch, plane, (int) N, (int) (N / 2), -1, 0)) break;  // along z, rows ky < N/2
+            if (any_lines(ph, d_phi, ph->AL.pitch, (long long) N * N, 0)) break;
+            if (any_cols(ph, false, d_phi, plane, ph->AL.pitch, (int) N, (int) N, -1, 0)) break;
+            if (any_cols(ph, false, d_phi, ph->AL.pitch, plane, (int) N, (int) (N / 2), -1, 0)) break;  // along z, rows ky < N/2
             if (zd::launch_any_phik(ph->AL, d_phi, *d_phik, 0)) break;
             if (hipDeviceSynchronize() != hipSuccess) break;
             frc = 0;
@@ -702,6 +761,17 @@ static int make_phik(const zd_params *p, const zd_pk *pk, cplx **d_phik) {
 }
 
 static zd::StoreLayout layout_for_chunks(const zd_plan *pl, int chunk_planes);
+
+// twiddles of a composite transform (zd_fft_q.h) of length len = P * Q: exp(2 pi i k / P) | exp(2 pi i k / len) | exp(2 pi i k / Q)
+static int upload_twq(int len, cplx **dst) {
+    int P = 0, Q = 0;
+    if (!zd::np2_split(len, &P, &Q)) return 1;
+    std::vector<cplx> t = make_twiddles(P), b = make_twiddles(len), c = make_twiddles(Q);
+    t.insert(t.end(), b.begin(), b.end());
+    t.insert(t.end(), c.begin(), c.end());
+    if (hipMalloc((void **) dst, sizeof(cplx) * t.size()) != hipSuccess) return 1;
+    return hipMemcpy(*dst, t.data(), sizeof(cplx) * t.size(), hipMemcpyHostToDevice) != hipSuccess;
+}
 
 // ---- f_NL on several ranks (zd_multi.cpp): the plans of the phi round and of the main pass, and the stages of the phi round
 // on a plane group / on the returned store ----
@@ -784,8 +854,9 @@ static int plan_create_one(const zd_params *p, const zd_pk *pk, const double *ei
                            int phi_mode, const cplx *phik, zd_plan **out) {
     const int64_t N = p->ppd;
     // Three transform families: powers of two (zd_kernels.hip), 2^a 3^b on the field stores (zd_kernels_np2.hip), and ANY
-    // other even PPD — or a 2^a 3^b one with options the composite kernels lack — as convolutions on the power-of-two engine
-    // (zd_kernels_any.hip: reference arrays, one rank, no f_NL)
+    // other even PPD — or a 2^a 3^b one with options the composite kernels lack — on the reference arrays, one rank
+    // (zd_kernels_any.hip).  Those lines are convolutions on the power-of-two engine, but for ZD_f_NL on a 2^a 3^b grid
+    // (fnl_np2): composite transforms there (zd_kernels_np2_ref.hip)
     const bool pow2 = is_pow2(N);
     bool any_path = false;
     int np2_R = 2;
@@ -1013,16 +1084,7 @@ static int plan_create_one(const zd_params *p, const zd_pk *pk, const double *ei
         PLCHECK(hipMalloc((void **) &pl->d_twL, sizeof(cplx) * twL.size()));
         PLCHECK(hipMemcpy(pl->d_twL, twL.data(), sizeof(cplx) * twL.size(), hipMemcpyHostToDevice));
         if (np2) {  // composite transforms (zd_fft_q.h): exp(2 pi i k / P) | exp(2 pi i k / len) | exp(2 pi i k / Q) per length
-            auto upload = [&](int len, cplx **dst) -> int {
-                int P = 0, Q = 0;
-                if (!zd::np2_split(len, &P, &Q)) return 1;
-                std::vector<cplx> t = make_twiddles(P), b = make_twiddles(len), c = make_twiddles(Q);
-                t.insert(t.end(), b.begin(), b.end());
-                t.insert(t.end(), c.begin(), c.end());
-                if (hipMalloc((void **) dst, sizeof(cplx) * t.size()) != hipSuccess) return 1;
-                return hipMemcpy(*dst, t.data(), sizeof(cplx) * t.size(), hipMemcpyHostToDevice) != hipSuccess;
-            };
-            if (upload(pl->N, &pl->d_twq_n) || upload(pl->L, &pl->d_twq_l)) {
+            if (upload_twq(pl->N, &pl->d_twq_n) || upload_twq(pl->L, &pl->d_twq_l)) {
                 fprintf(stderr, "zeldovich_hip: composite twiddle tables failed\n");
                 zd_plan_destroy(pl);
                 return 1;
@@ -1392,8 +1454,15 @@ static int plan_create_one(const zd_params *p, const zd_pk *pk, const double *ei
             }
         }
     }
-    if (any_path) {  // Bluestein tables for the z lines (length L) and the y / x lines (length N); simple [plane][array][y][x] store
-        if (any_make_tab(pl->L, &pl->tabL, pl->d_any) || any_make_tab(pl->N, &pl->tabN, pl->d_any + 3)) {
+    if (any_path) {  // simple [plane][array][y][x] store; tables for the z lines (length L) and the y / x lines (length N): composite
+                     // twiddles for f_NL on the composite grids (fnl_np2), Bluestein tables otherwise
+        if (fnl_np2(p, nranks) && fnl_np2_factor_ok(N, R)) {
+            if (upload_twq(pl->N, &pl->d_twr_n) || upload_twq(pl->L, &pl->d_twr_l)) {
+                fprintf(stderr, "zeldovich_hip: composite twiddle tables failed\n");
+                zd_plan_destroy(pl);
+                return 1;
+            }
+        } else if (any_make_tab(pl->L, &pl->tabL, pl->d_any) || any_make_tab(pl->N, &pl->tabN, pl->d_any + 3)) {
             zd_plan_destroy(pl);
             return 1;
         }
@@ -1435,6 +1504,8 @@ void zd_plan_destroy(zd_plan *pl) {
     hipFree(pl->d_v1err);
     hipFree(pl->d_phik_owned);
     for (cplx *b : pl->d_any) hipFree(b);
+    hipFree(pl->d_twr_n);
+    hipFree(pl->d_twr_l);
     for (cplx *y : pl->d_Y) hipFree(y);
     if (pl->s_gen) hipStreamDestroy(pl->s_gen);
     if (pl->s_fft) hipStreamDestroy(pl->s_fft);
@@ -1494,8 +1565,14 @@ static int any_stage_z(zd_plan *pl, int residue, void *d_send, hipStream_t st) {
             return 1;
         tick(pl, ZD_K_GEN, st, false);
         tick(pl, ZD_K_ZFFT, st, true);
-        if (zd::launch_any_cols(pl->tabL, pl->d_Y[0], (long long) pl->L * pl->N, pl->N, pl->N, pl->jobs.n * nky, -1, st)) return 1;
-        if (zd::launch_any_scatter(pl->jobs, pl->AL, r0, nky, pl->L, pl->d_Y[0], d_send, st)) return 1;
+        if (pl->phi_half) {  // phi round on half-space planes (one job, R = 1): the z lines straight into rows r0 .. of every plane
+            if (zd::launch_refq_cols_oop(pl->L, pl->d_twr_l, pl->d_Y[0], (long long) pl->L * pl->N, pl->N, (cplx *) d_send + (long long) r0 * pl->AL.pitch,
+                                         pl->AL.pitch, (long long) pl->half * pl->AL.pitch, pl->N, nky, false, st))
+                return 1;
+        } else {
+            if (any_cols(pl, true, pl->d_Y[0], (long long) pl->L * pl->N, pl->N, pl->N, pl->jobs.n * nky, -1, st)) return 1;
+            if (zd::launch_any_scatter(pl->jobs, pl->AL, r0, nky, pl->L, pl->d_Y[0], d_send, st)) return 1;
+        }
         tick(pl, ZD_K_ZFFT, st, false);
     }
     span_end(pl, zspan, st);
@@ -1690,7 +1767,7 @@ int zd_plan_stage_y_group(zd_plan *pl, void *d_recv, int chunk_planes, int nplan
     if (zd::pack_is_fields(pl->pack)) return 0;  // field stores: the y transform runs plane group by plane group in stage_x
     if (pl->any) {  // every (plane, array) image: columns along y, the Nyquist row counted as zero (zeldovich.cpp:644-650)
         tick(pl, ZD_K_YFFT, st, true);
-        if (zd::launch_any_cols(pl->tabN, d_recv, (long long) pl->N * pl->AL.pitch, pl->AL.pitch, pl->N, nplanes * pl->narray, pl->N / 2, st))
+        if (any_cols(pl, false, d_recv, (long long) pl->N * pl->AL.pitch, pl->AL.pitch, pl->N, nplanes * pl->narray, pl->N / 2, st))
             return 1;
         tick(pl, ZD_K_YFFT, st, false);
         return 0;
@@ -1729,7 +1806,7 @@ int zd_plan_stage_x_group(zd_plan *pl, int residue, const void *d_recv, int chun
         const int z_first = (int) zd_plan_plane_z(pl, residue, gplane0);
         cplx *first = (cplx *) const_cast<void *>(d_recv) + (long long) plane0 * pl->narray * pl->N * pl->AL.pitch;
         tick(pl, ZD_K_XFFT, st, true);
-        if (zd::launch_any_lines(pl->tabN, first, pl->AL.pitch, (long long) nplanes * pl->narray * pl->N, st)) return 1;
+        if (any_lines(pl, first, pl->AL.pitch, (long long) nplanes * pl->narray * pl->N, st)) return 1;
         if (zd::launch_any_emit(pl->AL, pl->ec, d_recv, (int) plane0, (int) nplanes, z_first, pl->R, d_records, d_density, pl->d_red, st)) return 1;
         tick(pl, ZD_K_XFFT, st, false);
         return 0;
@@ -1867,7 +1944,8 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
         if (make_phik(&p, pk, &d_phik)) return 1;
         HIPCHECK(hipMemGetInfo(&free_b, &total_b));
         if (p_in->stream_factor <= 0) {
-            const int R2 = zd_choose_stream_factor(&p, 1, (int64_t) free_b - ((int64_t) 16 << 30));
+            // (PhiK is allocated by now: it is part of what the chooser counts)
+            const int R2 = zd_choose_stream_factor(&p, 1, (int64_t) free_b - ((int64_t) 16 << 30) + fnl_phik_bytes(N));
             if (R2 < 0) {
                 hipFree(d_phik);
                 return 1;
@@ -2212,7 +2290,28 @@ static int test_fft_any(int32_t n, int64_t lines, int32_t axis_kind, const doubl
     return rc;
 }
 
+// the composite transforms of the reference's arrays (zd_kernels_np2_ref.hip), in place, any batch: axis_kind 3 = strided lines
+// (layout [n][lines], k_refq_cols), 4 = contiguous lines ([lines][n], k_refq_lines)
+static int test_fft_refq(int32_t n, int64_t lines, int32_t axis_kind, const double *in, double *out) {
+    cplx *d_tw = nullptr, *d = nullptr;
+    const size_t nb = sizeof(cplx) * (size_t) n * lines;
+    int rc = 1;
+    do {
+        if (!zd::refq_supported_len(n) || lines < 1 || lines > (1 << 20) || upload_twq(n, &d_tw)) break;
+        if (hipMalloc((void **) &d, nb) != hipSuccess) break;
+        if (hipMemcpy(d, in, nb, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (axis_kind == 3 ? zd::launch_refq_cols(n, d_tw, d, 0, lines, (int) lines, 1, -1, 0) : zd::launch_refq_lines(n, d_tw, d, n, lines, 0)) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(out, d, nb, hipMemcpyDeviceToHost) != hipSuccess) break;
+        rc = 0;
+    } while (0);
+    hipFree(d_tw);
+    hipFree(d);
+    return rc;
+}
+
 int zd_test_fft(int32_t n, int64_t lines, int32_t axis_kind, const double *in, double *out) {
+    if (axis_kind == 3 || axis_kind == 4) return test_fft_refq(n, lines, axis_kind, in, out);
     if (!is_pow2(n)) {
         int P = 0, Q = 0;
         // composite-length kernels where they exist and the batch is whole tiles; else the convolution kernels (any length,

@@ -110,6 +110,16 @@ int launch_any_emit(const AnyLayout &A, const EpiConst &ec, const void *store, i
                     float *density, Reduce *red, hipStream_t st);
 int launch_any_phi_nl(const AnyLayout &A, double f_NL, void *store, hipStream_t st);
 int launch_any_phik(const AnyLayout &A, const void *store, void *phik, hipStream_t st);
+// ---- composite-length transforms of the reference's arrays (zd_kernels_np2_ref.hip): ZD_f_NL on the composite grids ----
+// tw: exp(2 pi i k / P) | exp(2 pi i k / n) | exp(2 pi i k / Q) for n = P * Q (zd_fft_q.h); the arguments of launch_any_cols / _lines
+bool refq_supported_len(int n);
+int launch_refq_cols(int n, const void *tw, void *data, long long batch_stride, long long point_stride, int ncols, int nbatch, int zero_point,
+                     hipStream_t st);
+int launch_refq_lines(int n, const void *tw, void *data, long long pitch, long long nlines, hipStream_t st);
+int launch_refq_cols_oop(int n, const void *tw, const void *in, long long in_bs, long long in_ps, void *out, long long out_bs, long long out_ps,
+                         int ncols, int nbatch, bool conj, hipStream_t st);
+// ZD_f_NL phi round, half-space planes [z][ky < n/2][x] of pitch `pitch`: y inverse, phi + f_NL phi^2, y again (k_refq_yphi)
+int launch_refq_yphi(int n, const void *tw, void *store, long long pitch, int nplanes, double f_NL, hipStream_t st);
 // ---- ZD_Version = 1 streams (zd_kernels_v1.hip) ----
 int launch_v1_seed(unsigned long long seed, int block, V1Stream *streams, hipStream_t st);
 int launch_v1_draw(const GenConst &g, int block, int ky0, int ky_stride, int nrows, V1Stream *streams, void *dev, int *err,

@@ -88,6 +88,10 @@ struct zd_plan {
     zd::AnyTab tabL = {}, tabN = {};
     zd::AnyLayout AL = {};
     zdfft::cplx *d_any[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // ZD_f_NL on a composite grid (zd_kernels_np2_ref.hip): the same store and steps, the lines through the composite transforms
+    // (twiddle sets of zd_fft_q.h for the lengths N and L) instead of the Bluestein tables above
+    zdfft::cplx *d_twr_n = nullptr, *d_twr_l = nullptr;
+    bool phi_half = false;  // the phi round's Z stage writes the half-space planes [z][ky < N/2][x] (make_phik), no twin rows
     // timing
     std::vector<EventPair> events;
     std::vector<hipEvent_t> pool;

@@ -25,7 +25,9 @@ int zd_test_generate_loopback(const zd_params *p, const zd_pk *pk, const double 
  * regeneration the stream kernel uses (src/power_spectrum.cpp:18-25) */
 int zd_test_v1_words(int64_t seed, int32_t nblocks, uint32_t *out);
 /* batch of `lines` independent length-n inverse FFTs, host in/out [lines][n] complex double;
- * axis_kind 0: the contiguous-line kernel path (x pass), 1: the strided-line path (y/z passes) */
+ * axis_kind 0: the contiguous-line kernel path (x pass), 1: the strided-line path (y/z passes; host layout [n][lines]);
+ * 3 / 4: the composite transforms of the reference's arrays (ZD_f_NL on composite grids, zd_kernels_np2_ref.hip), strided lines
+ * (host layout [n][lines]) / contiguous lines, any n of its table and any number of lines */
 int zd_test_fft(int32_t n, int64_t lines, int32_t axis_kind, const double *in, double *out);
 /* on != 0: every store / exchange ring / phi field the library allocates from now on starts out as NaN bytes */
 void zd_test_poison(int on);
