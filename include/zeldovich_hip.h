@@ -30,8 +30,9 @@ enum { ZD_FMT_ZEL = 0, ZD_FMT_RVZEL = 1, ZD_FMT_RVDOUBLEZEL = 2, ZD_FMT_ZELSIMPL
 typedef struct zd_params {
     int64_t ppd;        /* cbrt(NP): a power of two in [32, 16384] (above 8192: ZA field store only; 8192 with PLT: its field store only, i.e. no ZD_qdensity / ZD_f_NL), or 2^a Q with a >= 5 and Q one of 3, 9, 27, 5, 15,
                          * 25, 45, 75, 125, 135, 7, 21, 35, 49 (sizes: csrc/zd_kernels_np2.hip NP2_SIZES; the composite-transform kernels: ZA and PLT, also with ZD_qdensity = 1 or 2 — PLT with a density on one rank per pass group), or ANY other even number in [8, 8192]
-                         * (one rank: convolution transforms on the power-of-two engine, ~6x slower).  ZD_f_NL on the composite sizes: one rank,
-                         * the reference's arrays with composite-length transforms (csrc/zd_kernels_np2_ref.hip) */
+                         * (one rank: convolution transforms on the power-of-two engine, ~6x slower).  ZD_f_NL on the composite sizes: the
+                         * reference's arrays with composite-length transforms (csrc/zd_kernels_np2_ref.hip), on one rank or split over several
+                         * (ZD_NumGPU = G, a power of two dividing PPD/2 and PPD/R; not with ZD_StoreMode = reference) */
     int32_t numblock;   /* ZD_NumBlock: v2 output does not depend on it; version 1: PPD / numblock random streams */
     int32_t cpd;        /* CPD: only used by the writer for ic_{z*cpd/ppd} */
     double boxsize;     /* BoxSize */
@@ -164,7 +165,9 @@ int zd_choose_pass_groups_measured(const zd_params *p, int ngpu, int64_t budget_
  * of the receive buffer (exactly torch.distributed.all_to_all_single / ncclAllToAll semantics).
  * With nranks == 1 the send buffer IS the receive buffer.
  * ZD_f_NL != 0 (one rank): zd_plan_create runs the phi round of the reference (src/zeldovich.cpp:945-960) once and the plan
- * keeps PhiK; its Z stages then read D = PhiK * M. */
+ * keeps PhiK; its Z stages then read D = PhiK * M.  On several ranks zd_generate (ZD_NumGPU) runs the phi round across them —
+ * powers of two up to 4096 and the composite sizes whose lines have composite transforms — each rank keeping PhiK of its rows
+ * (PPD^3 / (2 G) complex). */
 typedef struct zd_plan zd_plan;
 
 int zd_plan_create(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank,

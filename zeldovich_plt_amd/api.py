@@ -84,7 +84,7 @@ EXPORTED_SYMBOLS = [
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
-                   "zd_test_fft", "zd_test_poison"]
+                   "zd_test_fft", "zd_test_ycols", "zd_test_poison"]
 STORE_MODES = {"auto": 0, "reference": 1, "packed": 2, "fields": 3}  # zd_params.store_mode (ZD_STORE_*)
 
 _lib = None
@@ -130,6 +130,7 @@ def _load(path, testing):
         L.zd_test_modes_table.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), i64, vp, vp]
         L.zd_test_v1_words.argtypes = [i64, C.c_int32, vp]
         L.zd_test_fft.argtypes = [i32, i64, i32, vp, vp]
+        L.zd_test_ycols.argtypes = [i32, i32, i32, i32, i32, vp, vp]
         L.zd_test_poison.argtypes = [C.c_int]
         L.zd_test_poison.restype = None
     L.zd_choose_stream_factor.argtypes = [C.POINTER(ZdParams), C.c_int, i64]

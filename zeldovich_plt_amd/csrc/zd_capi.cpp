@@ -416,24 +416,51 @@ static bool np2_stream_factor_ok(int64_t N, int R) {
     return R >= 1 && (R == 1 || R % 2 == 0) && N % R == 0 && zd::np2_supported_zlen((int) (N / R));
 }
 
-// ZD_f_NL on a composite grid, one rank: the reference's arrays as on the convolution path (the second pass keeps the Nyquist
-// modes live, so the Hermitian field stores cannot carry it), every line through the composite transforms of
-// zd_kernels_np2_ref.hip where both line lengths — N (x, y; the phi round's z) and N / R (the z lines of a pass) — have one.
-// ZD_StoreMode = reference and ZD_qoneslab keep the convolution transforms, as does any stream factor outside fnl_np2_factor_ok.
-static bool fnl_np2(const zd_params *p, int nranks) {
-    return p->f_NL != 0. && nranks == 1 && !is_pow2(p->ppd) && zd::np2_supported_ppd((int) p->ppd) && p->store_mode != ZD_STORE_REFERENCE
+// ZD_f_NL on a composite grid: the reference's arrays as on the convolution path (the second pass keeps the Nyquist modes live,
+// so the Hermitian field stores cannot carry it), every line through the composite transforms of zd_kernels_np2_ref.hip where both
+// line lengths — N (x, y; the phi round's z) and N / R (the z lines of a pass) — have one.  One rank: ZD_StoreMode = reference and
+// ZD_qoneslab keep the convolution transforms, as does any stream factor outside fnl_np2_factor_ok.  Several ranks: the arrays split
+// over the ranks (AnyChunks) and nothing else — those configurations are refused (zd_fnl_multi_unsupported).
+static bool fnl_np2(const zd_params *p) {
+    return p->f_NL != 0. && !is_pow2(p->ppd) && zd::np2_supported_ppd((int) p->ppd) && p->store_mode != ZD_STORE_REFERENCE
            && p->qoneslab < 0 && !tune_env("ZD_NO_NP2_FNL");
 }
 static bool fnl_np2_factor_ok(int64_t N, int R) {
     return R >= 1 && N % R == 0 && zd::refq_supported_len((int) N) && zd::refq_supported_len((int) (N / R));
 }
+// (several ranks: the z lines of a pass, N / R, must deal out over the ranks too)
+static bool fnl_np2_multi_factor_ok(int64_t N, int R, int nranks) {
+    return fnl_np2_factor_ok(N, R) && (N / R) % nranks == 0 && (N / 2) % nranks == 0;
+}
+
+const char *zd_fnl_multi_unsupported(const zd_params *p) {
+    const int64_t N = p->ppd;
+    if (is_pow2(N)) return N > 4096 ? "ZD_f_NL != 0 on several GPUs needs PPD <= 4096 on the powers of two" : nullptr;
+    if (!zd::np2_supported_ppd((int) N) || !zd::refq_supported_len((int) N))
+        return "ZD_f_NL != 0 on several GPUs needs a PPD with composite transforms (2^a 3^b 5^c 7^d of the kernel table); this PPD runs "
+               "its lines as convolutions, on one GPU only";
+    if (p->store_mode == ZD_STORE_REFERENCE)
+        return "ZD_f_NL != 0 with ZD_StoreMode = reference runs the convolution transforms, on one GPU only";
+    if (p->qoneslab >= 0) return "ZD_f_NL != 0 with ZD_qoneslab runs the convolution transforms, on one GPU only";
+    if (tune_env("ZD_NO_NP2_FNL")) return "ZD_NO_NP2_FNL forces the convolution transforms, which run on one GPU only";
+    return nullptr;
+}
+
+// ZD_f_NL on a composite grid, several ranks: bytes per rank of the two-slot exchange ring of a store with `narray` arrays and Zq
+// planes per chunk (zd_plan_ring_bytes: a plane from every rank is narray N (N + pad) complex, ~4 GB per slot)
+static int64_t fnl_multi_ring_bytes(const zd_params *p, int narray, int64_t Zq) {
+    const int64_t N = p->ppd, per_plane = (int64_t) narray * N * (N + store_row_pad(N)) * 16;
+    int64_t gp = std::max<int64_t>(1, std::min<int64_t>(Zq, ((int64_t) 4 << 30) / per_plane));
+    if (p->exchange_planes > 0) gp = std::min<int64_t>(Zq, p->exchange_planes);
+    return 2 * per_plane * gp;
+}
 
 // ZD_f_NL memory: PhiK (half-space rows, [ky][kz][x]) and the phi round's planes — half-space rows on the composite transforms
 // (make_phik), the full store on the convolution ones
 static int64_t fnl_phik_bytes(int64_t N) { return (N / 2) * N * N * 16; }
-static int64_t fnl_phi_bytes(const zd_params *p, int nranks) {
+static int64_t fnl_phi_bytes(const zd_params *p) {
     const int64_t N = p->ppd;
-    return (fnl_np2(p, nranks) && fnl_np2_factor_ok(N, 1) ? N / 2 : N) * N * (N + store_row_pad(N)) * 16;
+    return (fnl_np2(p) && fnl_np2_factor_ok(N, 1) ? N / 2 : N) * N * (N + store_row_pad(N)) * 16;
 }
 
 // ZD_qdensity = 2 (density only): the displacement arrays are never built (src/zeldovich.cpp:303,440), so the eigenmodes of ZD_qPLT
@@ -499,16 +526,28 @@ static int choose_stream_factor_one(const zd_params *p, int nranks, int64_t budg
     // any other even PPD (or a 2^a 3^b one whose options the composite kernels lack): reference arrays on one rank, see
     // plan_create_ex; R any divisor of N
     auto any_factor = [&]() -> int {
-        if (N % 2 || N < 8 || N > 8192 || nranks != 1) return -1;
         const int64_t narray = p->qdensity == 2 ? 1 : (p->qPLT ? 4 : 2);
+        if (nranks > 1 && fnl_np2(p) && (N / 2) % nranks == 0) {
+            // f_NL on a composite grid, several ranks (the arrays split over them, AnyChunks).  Per rank: PhiK / G beside everything;
+            // the phi round's store / G (one array, every plane) and its ring before the main pass; each pass's store / G and ring
+            const int G = nranks;
+            const int64_t plane_b = N * (N + store_row_pad(N)) * 16, phik = fnl_phik_bytes(N) / G;  // (one array of a plane)
+            if (phik + N * plane_b / G + fnl_multi_ring_bytes(p, 1, N / G) > budget_bytes) return -1;
+            for (int R = 1; N / R >= 3; R++)
+                if (fnl_np2_multi_factor_ok(N, R, G)
+                    && phik + (N / R) * narray * plane_b / G + fnl_multi_ring_bytes(p, (int) narray, N / R / G) <= budget_bytes)
+                    return R;
+            return -1;
+        }
+        if (N % 2 || N < 8 || N > 8192 || nranks != 1) return -1;
         int64_t budget = budget_bytes;
         if (p->f_NL != 0.) {  // PhiK stays beside every pass's store; the phi round before it holds PhiK and the phi planes
             const int64_t phik = fnl_phik_bytes(N);
-            if (fnl_phi_bytes(p, nranks) + phik > budget) return -1;
+            if (fnl_phi_bytes(p) + phik > budget) return -1;
             budget -= phik;
         }
         // f_NL on a composite grid: the smallest factor whose z lines the composite transforms take (fnl_np2) comes first
-        for (int pass = fnl_np2(p, nranks) ? 0 : 1; pass < 2; pass++)
+        for (int pass = fnl_np2(p) ? 0 : 1; pass < 2; pass++)
             for (int R = 1; N / R >= 3; R++)  // any divisor of N (the z-residue fold is a plain decimation: R need not be 2^k here)
                 if (N % R == 0 && (pass == 1 || fnl_np2_factor_ok(N, R)) && (N / R) * narray * N * (N + store_row_pad(N)) * 16 <= budget)
                     return R;
@@ -761,6 +800,7 @@ static int make_phik(const zd_params *p, const zd_pk *pk, cplx **d_phik) {
 }
 
 static zd::StoreLayout layout_for_chunks(const zd_plan *pl, int chunk_planes);
+static zd::AnyChunks any_chunks(const zd_plan *pl, int chunk_planes);
 
 // twiddles of a composite transform (zd_fft_q.h) of length len = P * Q: exp(2 pi i k / P) | exp(2 pi i k / len) | exp(2 pi i k / Q)
 static int upload_twq(int len, cplx **dst) {
@@ -789,6 +829,15 @@ int zd_plan_create_phik(const zd_params *p, const zd_pk *pk, const double *eig, 
 // forward y — ZeldovichXY_Phi (zeldovich.cpp:699-790)
 int zd_plan_phi_xy_group(zd_plan *pl, void *d_slot, int chunk_planes, int nplanes, double f_NL, void *hip_stream) {
     hipStream_t st = (hipStream_t) hip_stream;
+    if (pl->any) {  // composite grid (AnyChunks): y inverse (the Nyquist row read as zero), x lines with phi + f_NL phi^2 (every row of
+                    // every chunk), y again — the rows ky < N/2 written back, all that the forward z lines into PhiK read
+        const zd::AnyChunks C = any_chunks(pl, chunk_planes);
+        if (zd::launch_refq_ycols(pl->N, pl->d_twr_n, C, d_slot, pl->N, nplanes, pl->N / 2, pl->N, st)) return 1;
+        for (int c = 0; c < pl->nranks; c++)
+            if (zd::launch_refq_xphi(pl->N, pl->d_twr_n, (cplx *) d_slot + c * C.chunk, C.pitch, (long long) nplanes * 2 * pl->Hq, f_NL, st))
+                return 1;
+        return zd::launch_refq_ycols(pl->N, pl->d_twr_n, C, d_slot, pl->N, nplanes, -1, pl->N / 2, st);
+    }
     const zd::StoreLayout S = layout_for_chunks(pl, chunk_planes);
     if (zd::launch_yfft(S, nplanes, pl->d_twN, d_slot, st)) return 1;
     if (zd::launch_fnl_stage(0, S, f_NL, pl->d_twN, d_slot, nullptr, nplanes, 0, st)) return 1;
@@ -796,6 +845,11 @@ int zd_plan_phi_xy_group(zd_plan *pl, void *d_slot, int chunk_planes, int nplane
 }
 // forward z over this rank's rows of the returned store -> PhiK[row slot][kz][x]
 int zd_plan_phi_zfwd(zd_plan *pl, void *d_store, void *d_phik, void *hip_stream) {
+    if (pl->any) {  // chunks are plane-major: plane z of this rank's rows sits at z (2 Hq pitch); conjugated, as make_phik does
+        const long long pitch = pl->AC.pitch;
+        return zd::launch_refq_cols_oop(pl->N, pl->d_twr_n, d_store, pitch, 2 * pl->Hq * pitch, d_phik, (long long) pl->N * pl->N, pl->N, pl->N,
+                                        pl->Hq, true, (hipStream_t) hip_stream);
+    }
     int lZq = 0;
     while ((1 << lZq) < pl->Zq) lZq++;
     return zd::launch_fnl_stage(2, pl->S, 0.0, pl->d_twN, d_store, d_phik, pl->N, lZq, (hipStream_t) hip_stream);
@@ -885,7 +939,17 @@ static int plan_create_one(const zd_params *p, const zd_pk *pk, const double *ei
     }
     int R = p->stream_factor > 0 ? p->stream_factor : 1;
     if (np2 && p->stream_factor <= 0) R = np2_R;
-    if (any_path) {
+    if (any_path && nranks > 1 && p->f_NL != 0.) {  // ZD_f_NL on a composite grid, the arrays split over the ranks (AnyChunks)
+        if (const char *why = zd_fnl_multi_unsupported(p)) {
+            fprintf(stderr, "zeldovich_hip: %s\n", why);
+            return 1;
+        }
+        if (!fnl_np2_multi_factor_ok(N, R, nranks)) {
+            fprintf(stderr, "zeldovich_hip: ZD_f_NL on %d ranks at PPD = %lld: stream factor %d has no composite z lines of length PPD / R "
+                            "dividing over the ranks\n", nranks, (long long) N, R);
+            return 1;
+        }
+    } else if (any_path) {
         if (N % 2 || N < 8 || N > 8192 || nranks != 1 || R < 1 || N % R || N / R < 3) {
             fprintf(stderr, "zeldovich_hip: PPD = %lld (neither 2^a nor a supported 2^a 3^b configuration) runs as convolutions on the "
                             "power-of-two engine: even PPD in [8, 8192], one rank, ZD_StreamFactor any divisor of PPD (got %d)\n",
@@ -1456,7 +1520,7 @@ static int plan_create_one(const zd_params *p, const zd_pk *pk, const double *ei
     }
     if (any_path) {  // simple [plane][array][y][x] store; tables for the z lines (length L) and the y / x lines (length N): composite
                      // twiddles for f_NL on the composite grids (fnl_np2), Bluestein tables otherwise
-        if (fnl_np2(p, nranks) && fnl_np2_factor_ok(N, R)) {
+        if (fnl_np2(p) && fnl_np2_factor_ok(N, R)) {
             if (upload_twq(pl->N, &pl->d_twr_n) || upload_twq(pl->L, &pl->d_twr_l)) {
                 fprintf(stderr, "zeldovich_hip: composite twiddle tables failed\n");
                 zd_plan_destroy(pl);
@@ -1470,6 +1534,11 @@ static int plan_create_one(const zd_params *p, const zd_pk *pk, const double *ei
         pl->AL.pitch     = pl->N + store_row_pad(pl->N);
         pl->AL.narray    = pl->narray;
         pl->store_bytes_ = (int64_t) pl->L * pl->narray * pl->N * pl->AL.pitch * 16;
+        if (nranks > 1) {  // [chunk = peer rank][local plane][array][row slot < 2 Hq][x]: 1 / G of the one-rank store
+            pl->AC           = zd::AnyChunks{pl->N, pl->AL.pitch, pl->narray, nranks, pl->Hq, pl->Zq, 0};
+            pl->AC.chunk     = (long long) pl->Zq * pl->narray * 2 * pl->Hq * pl->AL.pitch;
+            pl->store_bytes_ = (int64_t) nranks * pl->AC.chunk * 16;
+        }
     }
 #undef PLCHECK
     *out = pl;
@@ -1549,19 +1618,22 @@ static int any_stage_z(zd_plan *pl, int residue, void *d_send, hipStream_t st) {
     const int zspan = span_begin(pl, ZD_K_ZSTAGE, st);
     if (pl->v1_block && zd::launch_v1_seed((unsigned long long) pl->p.seed, pl->v1_block, pl->d_v1streams, st)) return 1;
     HIPCHECK(hipMemsetAsync(pl->d_tilectr, 0, sizeof(unsigned) * pl->n_tilectr, st));
+    const int ky_first = pl->rank, G = pl->nranks;  // this rank's half-space rows: rank, rank + G, ... (one rank: every row)
     int slab = 0;
     for (int r0 = 0; r0 < pl->Hq; r0 += pl->slab_rows, slab++) {
         const int nky = std::min(pl->slab_rows, pl->Hq - r0);
         tick(pl, ZD_K_GEN, st, true);
-        if (pl->v1_block)  // ZD_Version = 1: rows that share a stream are drawn by successive launches (zd_plan_stage_z)
-            for (int i0 = 0; i0 < nky; i0 += pl->v1_block)
-                if (zd::launch_v1_draw(pl->g, pl->v1_block, r0 + i0, 1, std::min(pl->v1_block, nky - i0), pl->d_v1streams,
+        if (pl->v1_block) {  // ZD_Version = 1: rows that share a stream are drawn by successive launches (zd_plan_stage_z)
+            const int group = pl->v1_block / G;
+            for (int i0 = 0; i0 < nky; i0 += group)
+                if (zd::launch_v1_draw(pl->g, pl->v1_block, ky_first + G * (r0 + i0), G, std::min(group, nky - i0), pl->d_v1streams,
                                        pl->d_v1dev + (size_t) i0 * pl->N * pl->N, pl->d_v1err, st))
                     return 1;
+        }
         // (k_genf with walks of 16 / 4 / 2 z rows where the kernel exists, else the general generator)
-        if (pl->d_eiglines && zd::launch_eig_lines(pl->g, r0, 1, nky, pl->d_eiglines, st)) return 1;
-        if (zd::launch_gen(pl->g, pl->J, pl->jobs, pl->S, r0, nky, pl->L, residue, residue, pl->d_twN, pl->d_Y[0], pl->d_tilectr + slab,
-                           pl->gen_max_wgs, st))
+        if (pl->d_eiglines && zd::launch_eig_lines(pl->g, ky_first + G * r0, G, nky, pl->d_eiglines, st)) return 1;
+        if (zd::launch_gen(pl->g, pl->J, pl->jobs, pl->S, ky_first + G * r0, nky, pl->L, residue, residue, pl->d_twN, pl->d_Y[0],
+                           pl->d_tilectr + slab, pl->gen_max_wgs, st))
             return 1;
         tick(pl, ZD_K_GEN, st, false);
         tick(pl, ZD_K_ZFFT, st, true);
@@ -1571,7 +1643,9 @@ static int any_stage_z(zd_plan *pl, int residue, void *d_send, hipStream_t st) {
                 return 1;
         } else {
             if (any_cols(pl, true, pl->d_Y[0], (long long) pl->L * pl->N, pl->N, pl->N, pl->jobs.n * nky, -1, st)) return 1;
-            if (zd::launch_any_scatter(pl->jobs, pl->AL, r0, nky, pl->L, pl->d_Y[0], d_send, st)) return 1;
+            if (G > 1 ? zd::launch_refq_scatter(pl->jobs, pl->AC, ky_first, r0, nky, pl->L, pl->d_Y[0], d_send, st)
+                      : zd::launch_any_scatter(pl->jobs, pl->AL, r0, nky, pl->L, pl->d_Y[0], d_send, st))
+                return 1;
         }
         tick(pl, ZD_K_ZFFT, st, false);
     }
@@ -1755,6 +1829,11 @@ static zd::StoreLayout layout_for_chunks(const zd_plan *pl, int chunk_planes) {
     }
     return S;
 }
+static zd::AnyChunks any_chunks(const zd_plan *pl, int chunk_planes) {
+    zd::AnyChunks C = pl->AC;
+    C.chunk         = (long long) chunk_planes * pl->narray * 2 * pl->Hq * pl->AC.pitch;
+    return C;
+}
 static zd::FieldLayout fields_for_chunks(const zd_plan *pl, int chunk_planes) {
     zd::FieldLayout F = pl->F;
     F.chunk_elems     = (long long) chunk_planes * F.nfield * F.field_elems;
@@ -1767,7 +1846,11 @@ int zd_plan_stage_y_group(zd_plan *pl, void *d_recv, int chunk_planes, int nplan
     if (zd::pack_is_fields(pl->pack)) return 0;  // field stores: the y transform runs plane group by plane group in stage_x
     if (pl->any) {  // every (plane, array) image: columns along y, the Nyquist row counted as zero (zeldovich.cpp:644-650)
         tick(pl, ZD_K_YFFT, st, true);
-        if (any_cols(pl, false, d_recv, (long long) pl->N * pl->AL.pitch, pl->AL.pitch, pl->N, nplanes * pl->narray, pl->N / 2, st))
+        if (pl->nranks > 1) {  // the columns gathered over the chunks of the ring slot
+            if (zd::launch_refq_ycols(pl->N, pl->d_twr_n, any_chunks(pl, chunk_planes), d_recv, pl->N, nplanes * pl->narray, pl->N / 2, pl->N,
+                                    st))
+                return 1;
+        } else if (any_cols(pl, false, d_recv, (long long) pl->N * pl->AL.pitch, pl->AL.pitch, pl->N, nplanes * pl->narray, pl->N / 2, st))
             return 1;
         tick(pl, ZD_K_YFFT, st, false);
         return 0;
@@ -1802,6 +1885,19 @@ int zd_plan_stage_x_group(zd_plan *pl, int residue, const void *d_recv, int chun
         d_density = nullptr;
     }
     if (d_density && pl->pack != zd::PACK_NONE && !pl->dens) return 1;  // packed stores carry no density field (but the six-field store)
+    if (pl->any && pl->nranks > 1) {  // the same on a chunked ring slot: x lines per chunk, the epilogue finds row y by its slot
+        const int z_first = (int) zd_plan_plane_z(pl, residue, gplane0);
+        const zd::AnyChunks C = any_chunks(pl, chunk_planes);
+        const long long img_rows = (long long) pl->narray * 2 * pl->Hq;
+        tick(pl, ZD_K_XFFT, st, true);
+        for (int c = 0; c < pl->nranks; c++)
+            if (zd::launch_refq_lines(pl->N, pl->d_twr_n, (cplx *) const_cast<void *>(d_recv) + c * C.chunk + plane0 * img_rows * C.pitch,
+                                      C.pitch, nplanes * img_rows, st))
+                return 1;
+        if (zd::launch_refq_emit(C, pl->ec, d_recv, (int) plane0, (int) nplanes, z_first, pl->R, d_records, d_density, pl->d_red, st)) return 1;
+        tick(pl, ZD_K_XFFT, st, false);
+        return 0;
+    }
     if (pl->any) {  // x lines of the planes in place (each plane once), then the particle epilogue
         const int z_first = (int) zd_plan_plane_z(pl, residue, gplane0);
         cplx *first = (cplx *) const_cast<void *>(d_recv) + (long long) plane0 * pl->narray * pl->N * pl->AL.pitch;
@@ -2303,6 +2399,42 @@ static int test_fft_refq(int32_t n, int64_t lines, int32_t axis_kind, const doub
         if (axis_kind == 3 ? zd::launch_refq_cols(n, d_tw, d, 0, lines, (int) lines, 1, -1, 0) : zd::launch_refq_lines(n, d_tw, d, n, lines, 0)) break;
         if (hipDeviceSynchronize() != hipSuccess) break;
         if (hipMemcpy(out, d, nb, hipMemcpyDeviceToHost) != hipSuccess) break;
+        rc = 0;
+    } while (0);
+    hipFree(d_tw);
+    hipFree(d);
+    return rc;
+}
+
+// the y columns of the arrays split over G ranks (k_refq_ycols) on host columns [image][ky][ncols]: the rows go to a chunked store of
+// `nimg` planes per chunk (row pitch ncols) by the map of any_chunk_row, are transformed, and come back the same way.  mode 0: ky = N/2
+// read as zero, every output written (the main pass, the phi round's first y transform); 1: every input read, outputs ky < N/2 only
+// (the phi round's second y transform) — the other rows of `out` keep their input
+int zd_test_ycols(int32_t n, int32_t G, int32_t ncols, int32_t nimg, int32_t mode, const double *in, double *out) {
+    cplx *d_tw = nullptr, *d = nullptr;
+    const size_t nel = (size_t) nimg * n * ncols;
+    int rc = 1;
+    do {
+        if (!zd::refq_supported_len(n) || G < 1 || (G & (G - 1)) || (n / 2) % G || ncols < 1 || nimg < 1 || nel > ((size_t) 1 << 26)) break;
+        if (upload_twq(n, &d_tw) || hipMalloc((void **) &d, sizeof(cplx) * nel) != hipSuccess) break;
+        zd::AnyChunks C{n, ncols, 1, G, n / (2 * G), nimg, 0};
+        C.chunk = (long long) nimg * 2 * C.Hq * ncols;
+        const cplx *hin = (const cplx *) in;
+        std::vector<cplx> h(nel);
+        auto at = [&](int b, int y) -> size_t {
+            int c = 0, sl = 0;
+            zd::any_chunk_row(C, y, c, sl);
+            return (size_t) (c * C.chunk + ((long long) b * 2 * C.Hq + sl) * ncols);
+        };
+        for (int b = 0; b < nimg; b++)
+            for (int y = 0; y < n; y++) std::copy(hin + ((size_t) b * n + y) * ncols, hin + ((size_t) b * n + y + 1) * ncols, h.begin() + at(b, y));
+        if (hipMemcpy(d, h.data(), sizeof(cplx) * nel, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (zd::launch_refq_ycols(n, d_tw, C, d, ncols, nimg, mode == 0 ? n / 2 : -1, mode == 0 ? n : n / 2, 0)) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(h.data(), d, sizeof(cplx) * nel, hipMemcpyDeviceToHost) != hipSuccess) break;
+        cplx *hout = (cplx *) out;
+        for (int b = 0; b < nimg; b++)
+            for (int y = 0; y < n; y++) std::copy(h.begin() + at(b, y), h.begin() + at(b, y) + ncols, hout + ((size_t) b * n + y) * ncols);
         rc = 0;
     } while (0);
     hipFree(d_tw);

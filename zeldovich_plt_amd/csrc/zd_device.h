@@ -293,6 +293,23 @@ struct AnyTab {
 struct AnyLayout {  // store [plane][array][row y][x]
     int N, pitch, narray;
 };
+// The same arrays split over G ranks (ZD_f_NL on the composite grids, several ranks; zd_kernels_np2_ref.hip), the chunk semantics of
+// StoreLayout: [chunk][local plane][array][row slot][x], row pitch `pitch`.  Rank g owns the half-space rows ky = g + G i at slot i < Hq
+// and their twins N - ky at slot Hq + i; the unused twin slot of ky = 0 holds the Nyquist row ky = N/2, never read.  In a send store
+// chunk c holds the planes c Zq ... c Zq + Zq - 1 of this rank's rows; in a ring slot chunk s holds rank s's rows of the group's
+// planes.  G is a power of two; Hq = N / (2G) and Zq = L / G need not be (plain division).
+struct AnyChunks {
+    int N, pitch, narray;
+    int G, Hq, Zq;
+    long long chunk;  // elements per chunk: (planes per chunk) * narray * 2 Hq * pitch
+};
+// chunk and row slot of row y (ky or, after the y transform, y) of an AnyChunks store
+ZD_HD void any_chunk_row(const AnyChunks &C, int y, int &chunk, int &slot) {
+    const int half = C.N / 2;
+    const int h = y < half ? y : (y == half ? 0 : C.N - y), tw = y < half ? 0 : 1;
+    chunk = h & (C.G - 1);
+    slot  = h / C.G + tw * C.Hq;
+}
 
 // device-side reductions (output.cpp:28-30,190-197): NSLOT replicated accumulators
 constexpr int NSLOT = 64;

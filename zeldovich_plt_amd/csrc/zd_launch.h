@@ -120,6 +120,14 @@ int launch_refq_cols_oop(int n, const void *tw, const void *in, long long in_bs,
                          int ncols, int nbatch, bool conj, hipStream_t st);
 // ZD_f_NL phi round, half-space planes [z][ky < n/2][x] of pitch `pitch`: y inverse, phi + f_NL phi^2, y again (k_refq_yphi)
 int launch_refq_yphi(int n, const void *tw, void *store, long long pitch, int nplanes, double f_NL, hipStream_t st);
+// several ranks (AnyChunks store): z lines into the send store, y columns over the chunks (point ky = zero_point read as zero, outputs
+// k >= out_limit not written), the phi round's x lines (inverse, phi + f_NL phi^2, again), the particle epilogue
+int launch_refq_scatter(const JobList &jobs, const AnyChunks &C, int ky_first, int r0, int nky, int L, const void *Y, void *store, hipStream_t st);
+int launch_refq_ycols(int n, const void *tw, const AnyChunks &C, void *data, int ncols, int nbatch, int zero_point, int out_limit,
+                      hipStream_t st);
+int launch_refq_xphi(int n, const void *tw, void *data, long long pitch, long long nlines, double f_NL, hipStream_t st);
+int launch_refq_emit(const AnyChunks &C, const EpiConst &ec, const void *store, int plane0, int nplanes, int z_first, int z_step, void *records,
+                     float *density, Reduce *red, hipStream_t st);
 // ---- ZD_Version = 1 streams (zd_kernels_v1.hip) ----
 int launch_v1_seed(unsigned long long seed, int block, V1Stream *streams, hipStream_t st);
 int launch_v1_draw(const GenConst &g, int block, int ky0, int ky_stride, int nrows, V1Stream *streams, void *dev, int *err,

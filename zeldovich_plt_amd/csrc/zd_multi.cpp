@@ -955,10 +955,11 @@ int zd_generate_multi(const zd_params *p_in, const zd_pk *pk, const double *eig,
         fprintf(stderr, "zeldovich_hip: no GPU\n");
         return 1;
     }
-    if (p_in->f_NL != 0. && (p_in->ppd > 4096 || (p_in->ppd & (p_in->ppd - 1)))) {
-        fprintf(stderr, "zeldovich_hip: ZD_f_NL != 0 on several GPUs needs a power-of-two PPD <= 4096 (the z lines of the phi round are not "
-                        "streamed)\n");
-        return 1;
+    if (p_in->f_NL != 0.) {  // powers of two up to 4096 and the composite grids with composite transforms (the arrays split over the ranks)
+        if (const char *why = zd_fnl_multi_unsupported(p_in)) {
+            fprintf(stderr, "zeldovich_hip: %s\n", why);
+            return 1;
+        }
     }
     if (transport == 0 && ndev < G) {
         fprintf(stderr, "zeldovich_hip: ZD_NumGPU = %d but only %d GPU(s) are visible\n", G, ndev);
@@ -973,8 +974,10 @@ int zd_generate_multi(const zd_params *p_in, const zd_pk *pk, const double *eig,
         size_t free_b = 0, total_b = 0;
         MHIP(hipMemGetInfo(&free_b, &total_b));
         const int ranks_per_dev = (G + ndev - 1) / ndev;
-        // (ZD_f_NL: every rank also keeps PhiK of its rows, N^3 / (2 G) complex)
-        const int64_t phik_b = p.f_NL != 0. ? (p.ppd / 2 / G) * p.ppd * p.ppd * 16 : 0;
+        // (ZD_f_NL on the powers of two: every rank also keeps PhiK of its rows, N^3 / (2 G) complex; on the composite grids the
+        // chooser counts it itself, with the phi round's peak)
+        const bool pow2 = (p.ppd & (p.ppd - 1)) == 0;
+        const int64_t phik_b = p.f_NL != 0. && pow2 ? (p.ppd / 2 / G) * p.ppd * p.ppd * 16 : 0;
         int32_t g = 1, R = 0;
         if (zd_choose_pass_groups(&p, G, ((int64_t) free_b - ((int64_t) 16 << 30)) / ranks_per_dev - phik_b, &g, &R)) {
             fprintf(stderr, "zeldovich_hip: PPD %lld does not fit %d GPU(s)\n", (long long) p.ppd, G);

@@ -92,6 +92,9 @@ struct zd_plan {
     // (twiddle sets of zd_fft_q.h for the lengths N and L) instead of the Bluestein tables above
     zdfft::cplx *d_twr_n = nullptr, *d_twr_l = nullptr;
     bool phi_half = false;  // the phi round's Z stage writes the half-space planes [z][ky < N/2][x] (make_phik), no twin rows
+    // the same arrays split over several ranks (nranks > 1): the chunked store of zd_device.h AnyChunks (chunk = Zq planes; a ring
+    // slot of chunk_planes planes per chunk only changes AC.chunk)
+    zd::AnyChunks AC = {};
     // timing
     std::vector<EventPair> events;
     std::vector<hipEvent_t> pool;
@@ -111,6 +114,8 @@ int zd_plan_create_phik(const zd_params *p, const zd_pk *pk, const double *eig, 
                         zd_plan **out);
 int zd_plan_phi_xy_group(zd_plan *pl, void *d_slot, int chunk_planes, int nplanes, double f_NL, void *hip_stream);
 int zd_plan_phi_zfwd(zd_plan *pl, void *d_store, void *d_phik, void *hip_stream);
+// NULL if ZD_f_NL with these parameters runs on several ranks, else why not
+const char *zd_fnl_multi_unsupported(const zd_params *p);
 // hipEvent pair around something on `hip_stream` that is not a kernel of this file (zd_multi.cpp: the wait for an exchanged
 // plane group); summed into kernel_ms[kind] by zd_plan_stats when the plan profiles
 void zd_plan_tick(zd_plan *pl, int kind, void *hip_stream, int begin);

@@ -29,6 +29,10 @@ int zd_test_v1_words(int64_t seed, int32_t nblocks, uint32_t *out);
  * 3 / 4: the composite transforms of the reference's arrays (ZD_f_NL on composite grids, zd_kernels_np2_ref.hip), strided lines
  * (host layout [n][lines]) / contiguous lines, any n of its table and any number of lines */
 int zd_test_fft(int32_t n, int64_t lines, int32_t axis_kind, const double *in, double *out);
+/* the y columns of the reference's arrays split over G ranks (ZD_f_NL on composite grids, several ranks: k_refq_ycols) on host
+ * columns [nimg][n][ncols] complex double, through a chunked store of nimg planes per chunk; mode 0: ky = n/2 read as zero, every
+ * output written; 1: every input read, outputs ky < n/2 only (the other rows of out keep their input) */
+int zd_test_ycols(int32_t n, int32_t G, int32_t ncols, int32_t nimg, int32_t mode, const double *in, double *out);
 /* on != 0: every store / exchange ring / phi field the library allocates from now on starts out as NaN bytes */
 void zd_test_poison(int on);
 /* rank >= 0: that rank of the thread-per-GPU driver (zd_generate with ngpu > 1, zd_test_generate_loopback) fails BEFORE its first
