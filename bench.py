@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — grid->displacements throughput of the MI355X path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--ppd P] [--plt 0|1] [--format RVZel] [--stream R] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--ppd P] [--plt 0|1] [--format RVZel] [--stream R] [--dump-outputs DIR] [--full]
 
 One "step" = one complete pass of the hot path over the workload: mode generation, Hermitian
 packing + z FFT, (all-to-all between ranks), y FFT, x FFT + particle epilogue for all ppd^3
@@ -12,8 +12,11 @@ the fixed workload is sharded over the ranks ("strong" scaling) with ONE exchang
 pass between the Z and XY stages, done inside the library in plane groups over RCCL and overlapped with the XY stages.
 
 Prints ONE JSON line on rank 0 (see the contract in the task statement) with `roofline`
-(dominant kernel, hipEvent-timed on the launch stream inside the timed region) and
-`cpu_baseline` (the oracle — CPU port of the reference — timed on the host cores, rank 0, N=1).
+(dominant kernel, hipEvent-timed on the launch stream inside the timed region).  A plain run does
+only that: set up, warm up, time the K steps, dump, print.  `--full` adds the measurements that take
+runs of their own: `kernels_isolated` (one untimed pass with every kernel alone on the chip, N=1),
+`cpu_baseline` (the oracle — CPU port of the reference — timed on the host cores, rank 0, N=1) and,
+on the N > 1 code path, the other split of the GPUs (`modes`).
 """
 import argparse
 import json
@@ -237,14 +240,17 @@ def main():
     # it runs on ONE GPU through z-residue streaming (R=8).  --ppd 2048 --plt 1 is configs[2].
     ap.add_argument("--ppd", type=int, default=int(os.environ.get("ZD_BENCH_PPD", "4096")))
     ap.add_argument("--plt", type=int, default=int(os.environ.get("ZD_BENCH_PLT", "0")))
-    ap.add_argument("--no-isolated", action="store_true", help="skip the extra untimed pass that times every kernel alone")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run what takes runs of its own: the untimed pass that times every "
+                         "kernel alone, the CPU baseline and (N > 1 code path) the other split of the GPUs")
+    ap.add_argument("--no-isolated", action="store_true", help="--full: skip the extra untimed pass that times every kernel alone")
     ap.add_argument("--format", default="RVZel")
     ap.add_argument("--stream", type=int, default=0, help="z-residue stream factor R (0 = auto)")
     ap.add_argument("--groups", type=int, default=0,
                     help="N > 1: independent groups of GPUs, residue passes dealt round-robin over them (0 = the library's choice: "
                          "one GPU per group while the passes, after at most one doubling of the stream factor, deal out over the N GPUs; else "
                          "one group with the all-to-all exchange)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--store-mode", default=os.environ.get("ZD_BENCH_STORE_MODE", "auto") or "auto",
                     help="zd_params.store_mode for A/B runs (auto | reference | packed | fields): PLT with `packed` keeps the two-kernel "
                          "Z stage where `auto` takes the fused generator + z FFT")
@@ -437,10 +443,10 @@ def main():
         dump_outputs(args.dump_outputs, main_mode["records"])
         main_mode["records"] = None
 
-    # one extra UNTIMED pass with the two-stream overlap of the Z stage switched off: every kernel alone on the chip
+    # --full: one extra UNTIMED pass with the two-stream overlap of the Z stage switched off: every kernel alone on the chip
     # (in the timed region k_gen and k_zfft share it, so their hipEvent spans there include each other)
     iso = None
-    if world == 1 and not args.no_isolated:
+    if args.full and world == 1 and not args.no_isolated:
         p.serial_z = 1
         plan_iso = zd.Plan(p, ps, eig=eig, rank=0, nranks=1)
         p.serial_z = 0
@@ -573,15 +579,15 @@ def main():
             out["exchange"] = {"transport": "RCCL grouped ncclSend/ncclRecv per plane group (zd_plan_run_pass)",
                                "GB_per_step_all_ranks": sum(r["GB_sent_per_step"] for r in per_rank),
                                "max_exchange_wait_ms": max(r["exchange_wait_ms"] for r in per_rank)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(N, plt, fmt, eig)
             except Exception as e:  # the baseline is a reported number, never the product path
                 out["cpu_baseline"] = {"value": None, "unit": "particles/s", "cores": os.cpu_count(), "kind": "port",
                                        "sample": "failed: %r" % (e,)}
-    # N > 1 (or --dist): the OTHER way to share the job is timed in the same run, so that one SCALE record holds both — BASELINE C4
-    # names the slab all-to-all ("one group of all GPUs"), the library's default for PPD=4096 is one GPU per pass group with no
-    # exchange at all; `value` is the default's, `modes` has both with per-rank spans and bytes
+    # N > 1 (or --dist) with --full: the OTHER way to share the job is timed in the same run, so that one SCALE record holds both —
+    # BASELINE C4 names the slab all-to-all ("one group of all GPUs"), the library's default for PPD=4096 is one GPU per pass group
+    # with no exchange at all; `value` is the default's, `modes` has both with per-rank spans and bytes (a plain run: the default's)
     modes = None
     if multi:
         # a split is named by what happens between its GPUs: ranks of a group exchange (all_to_all) or every GPU is its own group
@@ -591,6 +597,7 @@ def main():
                  # what the default was chosen on: the probed rate of one link (all links of a GPU busy) and the library's estimate
                  # of a step for both splits at that rate (empty: only one split exists for this job, or nothing was measured)
                  "link_probe": link, "estimate_at_probed_rate": choice_est}
+    if multi and args.full:
         close_mode(main_mode)
         plan = comm = pipe = None
         other = None

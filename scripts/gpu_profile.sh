@@ -1,7 +1,7 @@
 # rocprofv3 evidence for the default bench workload (run through gpurun from the repo root):
 #   1. --kernel-trace --stats of `bench.py --steps 2 --warmup 1`      -> gpurun_out/prof_<TAG>/…kernel_stats.csv
 #   2. separate --pmc FETCH_SIZE / WRITE_SIZE passes (one step each)    -> per-kernel HBM bytes per launch
-#   3. a plain `python bench.py` (no profiler)                          -> gpurun_out/bench_<TAG>.json
+#   3. `python bench.py --full` (no profiler)                           -> profiles/<TAG>_bench.json
 # Summaries are copied to profiles/ by hand afterwards (profiles/README.md).
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
@@ -68,7 +68,7 @@ json.dump(out,open(f"{R}/gpurun_out/traffic_{TAG}.json","w"),indent=1)
 PY
 cat $(find $R/gpurun_out/prof_$TAG -name "*kernel_stats.csv" | head -1) | head -8 | cut -c1-200
 cp gpurun_out/traffic_$TAG.json profiles/traffic_latest.json
-timeout 900 python bench.py $ARGS 2>&1 | tail -1 > gpurun_out/bench_$TAG.json; python3 -c "
-import json;d=json.load(open('gpurun_out/bench_$TAG.json'));print(d['value'],d['ms_per_step'],d['roofline_path_frac']);print(d['cpu_baseline']);print(d['roofline']);print(d['kernels_isolated'])"
-# (everything stays under gpurun_out/, which gpurun merges back; the summaries are copied into profiles/ by hand afterwards)
+timeout 900 python bench.py --full $ARGS 2>&1 | tail -1 > profiles/${TAG}_bench.json; python3 -c "
+import json;d=json.load(open('profiles/${TAG}_bench.json'));print(d['value'],d['ms_per_step'],d['roofline_path_frac']);print(d['cpu_baseline']);print(d['roofline']);print(d['kernels_isolated'])"
+# (the traces and summaries stay in the run's output folder; the ones worth keeping are copied into profiles/ by hand afterwards)
 i=0; for f in $(find gpurun_out/prof_$TAG -name "*kernel_stats.csv" | sort); do cp $f gpurun_out/${TAG}_kernel_stats$([ $i -gt 0 ] && echo _$i).csv; i=$((i+1)); done

@@ -8,7 +8,7 @@ rm -f gpurun_out/z_store_merge gpurun_out/mall_handoff
 echo "== generator alone (isolated pass, serial_z) against its persistent workgroups per CU =="
 export ZD_LIB_PATH=$GRAFT_REPO_ROOT/zeldovich_plt_amd/csrc/build/libzeldovich_hip_tuning.so
 for w in 1 2 3 4; do
-  ZD_GEN_WGS=$w timeout -k 10 200 python bench.py --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  ZD_GEN_WGS=$w timeout -k 10 200 python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('GEN_WGS=$w step', round(d['ms_per_step']), {k: round(v['ms_per_step']) for k,v in d['kernels'].items()}, 'isolated', {k: round(v['ms_per_step']) for k,v in d['kernels_isolated'].items()})" || exit 1
 done
 unset ZD_LIB_PATH

@@ -33,7 +33,7 @@ def test_bench_distributed_code_path_on_one_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29531", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--ppd", "512",
-           "--dist", "--no-cpu-baseline", "--no-isolated"]
+           "--dist", "--full", "--no-cpu-baseline", "--no-isolated"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -68,7 +68,7 @@ def test_bench_keeps_its_line_when_the_second_split_is_killed():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", ZD_BENCH_SELFTEST_SIGNAL=str(int(signal.SIGTERM)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--ppd", "256",
-           "--dist", "--no-cpu-baseline", "--no-isolated"]
+           "--dist", "--full", "--no-cpu-baseline", "--no-isolated"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
