@@ -488,7 +488,9 @@ def test_fnl_round_trip_identity_at_large_sizes(zd, n, R):
     """The phi round of ZD_f_NL (inverse z / y / x transforms of phi = D / M, phi + f_NL phi^2, forward x / y / z transforms, D = phi M:
     k_xphi / k_yfwd / k_zfwd, launch_fnl_t<N>) at sizes the oracle cannot run: with f_NL = 1e-300 the nonlinear term vanishes and
     the second pass must reproduce the ordinary run — every record of sample planes to 1e-10 (src/zeldovich.cpp:699-790, 945-960).
-    PPD = 2048 is the largest size whose phi field (137 GB) fits one GPU."""
+    PPD = 2048 is the largest size whose phi field (137 GB) fits one GPU.
+    Not covered here: the phi^2 term itself (it vanishes) — a kernel that squares the wrong site, skips a plane or loses the second
+    pass's Nyquist-plane modes passes this test.  test_gpu_fnl_closed_form.py checks that term at these sizes against a closed form."""
     ps = zd.PowerSpectrum.from_file(WMAP, 720.0)
     zs = [3, n // 2 + 1]
     kw = dict(fmt="RVdoubleZel", stream_factor=R, n_s=0.96, Omega_M=0.31)

@@ -245,7 +245,9 @@ def test_fnl_round_trip_identity_at_large_composite_sizes(zd, ps, n):
     """PPD = 2304 = 256 * 9 and 2400 = 32 * 75 with f_NL = 1e-300 on one GPU: the nonlinear term vanishes, and the second pass must
     reproduce the ordinary composite ZA run — records of sample planes to 1e-10.  The phi round holds half-space planes beside PhiK
     (~8 N^3 + 8 N^3 bytes: 222 GB at 2400); the full phi store of the convolution path (16 N^3 + 8 N^3: 334 GB at 2400) does not fit
-    one MI355X at 2400 (at 2304 it peaks at 297 GB of the 309 GB)."""
+    one MI355X at 2400 (at 2304 it peaks at 297 GB of the 309 GB).
+    Not covered here: the phi^2 term itself (it vanishes with f_NL = 1e-300); test_gpu_fnl_closed_form.py checks it at 960 ... 2400
+    against a closed form with a second wave as large as the first."""
     zs, stride = [3, n // 2 + 1, n - 1], 4
     kw = dict(icformat="RVdoubleZel", n_s=0.96, Omega_M=0.31)
     a, _ = _sample_planes(zd, zd.make_params(n, **kw), zs, stride)
