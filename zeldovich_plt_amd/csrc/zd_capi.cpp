@@ -18,6 +18,7 @@
 #include "zd_device.h"
 #include "zd_launch.h"
 #include "zd_plan.h"
+#include "zd_route.h"
 #ifdef ZD_TUNING
 #include "zd_tuning.h"
 #endif
@@ -27,6 +28,9 @@
 
 using zdfft::cplx;
 using zdpcg::u128;
+using zd::is_pow2;
+using zd::Route;
+using zd::route;
 
 #define HIPCHECK(call)                                                                               \
     do {                                                                                             \
@@ -85,18 +89,6 @@ hipError_t zd_store_alloc(void **p, size_t bytes) {
 }
 
 namespace {
-
-
-bool is_pow2(int64_t n) { return n > 0 && (n & (n - 1)) == 0; }
-
-// Tuning / ablation knobs (environment variables ZD_ABLATE, ZD_PRUNE, ZD_NT, ZD_LAYOUT, ...) exist only in the
-// -DZD_TUNING build (make tuning -> build/libzeldovich_hip_tuning.so, used by scripts/ through ZD_LIB_PATH).
-// The product library never reads the environment: the names below do not even reach its binary.
-#ifdef ZD_TUNING
-const char *tune_env(const char *name) { return getenv(name); }
-#else
-#define tune_env(name) ((const char *) nullptr)
-#endif
 
 std::vector<cplx> make_twiddles(int n) {
     std::vector<cplx> tw(n);
@@ -294,50 +286,6 @@ zdpcg::Affine row_jump_full(long long drows) {  // 2*65536*drows draws
 
 extern "C" {
 
-// ZD_qdensity = 1 on the composite grids (PPD = 2^a 3^b 5^c 7^d; round 4): the ZA field store carries two more half-space sums — the
-// density D of the two residues of a pass — and the y / x stages add one array, delta_r0 + i delta_r1 (zd_kernels_np2.hip).  The
-// power-of-two grids keep the reference's arrays for ZD_qdensity (their kernels exist).  PLT with ZD_qdensity = 1 on a composite grid
-// is composed of a PLT run and density-only passes of this store (plt_dens_split); f_NL stays on the convolution path there.
-static bool dens_fields(const zd_params *p) {
-    // (8640 = 64 * 135 included: the six-field store runs there too — tests/test_gpu_baseline_regime.py,
-    // test_density_one_mode_at_every_composite_size[8640]; the PPD > 8192 gate's message says so)
-    // (ZD_qdensity = 2, density only — round 5: the same six-field store, the displacement arrays are simply not built and no records
-    // are written; the four potentials ride along unused, which still beats the convolution path by ~4x)
-    return (p->qdensity == 1 || p->qdensity == 2) && !p->qPLT && p->f_NL == 0. && p->qoneslab < 0 && !is_pow2(p->ppd) && zd::np2_supported_ppd((int) p->ppd)
-           && (p->store_mode == ZD_STORE_AUTO || p->store_mode == ZD_STORE_FIELDS);
-}
-// Packed stores (zd_device.h PACK_*): without ZD_qdensity the density field is not transformed.
-static int pack_mode(const zd_params *p, int R) {
-    if (p->store_mode == ZD_STORE_REFERENCE) return zd::PACK_NONE;
-    if ((p->qdensity != 0 && !dens_fields(p)) || p->f_NL != 0.) return zd::PACK_NONE;
-    if (p->qoneslab >= 0) return zd::PACK_NONE;  // density_variance is then the sum over that one slab (output.cpp:197)
-    {   // The packed stores treat every field as the transform of a REAL field (Hermitian modes) and take
-        // density_variance from sum |D|^2.  That needs every mode with a component on the Nyquist plane |k_i| = N/2 to
-        // be zero: the |k_i| == kmax rule does it when kmax == N/2 (k_cutoff = 1), the spherical cut when k_cutoff >= 1
-        // and CornerModes is off.  Otherwise (e.g. CornerModes with k_cutoff = 2) the reference keeps independent,
-        // non-Hermitian draws there and takes Re/Im of the mixed field (zeldovich.cpp:350-356): reference arrays.
-        const int half = (int) (p->ppd / 2), kmax = (int) ((double) half * (1.0 / p->k_cutoff) + .5);
-        const bool nyquist_dead = kmax == half || (!p->corner_modes && p->k_cutoff >= 1.0);
-        if (!nyquist_dead) return zd::PACK_NONE;
-    }
-    // PPD = 8192: three lines of a row no longer fit a workgroup of the x pass; only the field store has an x kernel that
-    // takes them in sequence (k_xfft_seq)
-    // PLT: the three packed arrays by default; its field store (six half-space sums) only on request — measured slower
-    // (PPD=2048 PLT+rescale 0.553 -> 0.609 s: every array of the y stage needs two potentials, each fetched twice, and the
-    // 148-VGPR PLT generator leaves no room for the z FFT beside it anyway)
-    // (PPD = 8192: the x pass of the packed arrays does not exist — three lines of a row are 1536 threads — so PLT runs on
-    // its field store there, whose ring goes through k_xfft_two)
-    // PPD = 2^a 3^b: the composite-transform kernels exist for the field stores only
-    if (p->qPLT) return (p->ppd > 4096 || !is_pow2(p->ppd) || p->store_mode == ZD_STORE_FIELDS) ? zd::PACK_PLTFIELD : zd::PACK_PLT3;
-    if (R < 2) return zd::PACK_NONE;  // the ZA packings carry two z-residues per pass
-    if (p->store_mode == ZD_STORE_PACKED) return p->ppd > 4096 ? zd::PACK_NONE : zd::PACK_ZAPAIR;
-    return zd::PACK_ZAFIELD;
-}
-static int store_arrays(const zd_params *p, int R) {
-    if (pack_mode(p, R) != zd::PACK_NONE) return 3;
-    return p->qdensity == 2 ? 1 : (p->qPLT ? 4 : 2);
-}
-
 // the zero rule of zeldovich.cpp:350-353 as the kernels prune by it (zd_device.h column_is_zero)
 static void prune_rule(const zd_params *p, zd::StoreLayout &S) {
     const int half = (int) (p->ppd / 2);
@@ -396,12 +344,13 @@ static int64_t field_rows(const zd_params *p, int nranks, std::vector<zd::FieldR
     return total;
 }
 
-// bytes of the block store one rank holds per pass (send side; nranks > 1 doubles it with the receive buffer)
+// bytes of the block store one rank holds per pass (send side; nranks > 1 doubles it with the receive buffer).  Priced for the store the
+// options ask for (pack_mode), also where the route demotes it or is refused: a finding (tests/test_route_agreement.py), kept
 static int64_t store_bytes(const zd_params *p, int R, int nranks) {
     const int64_t N = p->ppd;
-    const int pm = pack_mode(p, R);
-    if (zd::pack_is_fields(pm)) return (N / R) * (pm == zd::PACK_PLTFIELD ? 6 : (dens_fields(p) ? 6 : 4)) * field_rows(p, nranks, nullptr) * 16;
-    return N * (N + store_row_pad(N)) * (N / R) / nranks * 16 * store_arrays(p, R);
+    const int pm = zd::pack_mode(p, R);
+    if (zd::pack_is_fields(pm)) return (N / R) * (pm == zd::PACK_PLTFIELD || zd::dens_fields(p) ? 6 : 4) * field_rows(p, nranks, nullptr) * 16;
+    return N * (N + store_row_pad(N)) * (N / R) / nranks * 16 * (pm != zd::PACK_NONE ? 3 : zd::ref_arrays(p));
 }
 // ring between the y and x stages of the field store: planes of the three PACK_ZAPAIR arrays
 static int field_ring_planes(int64_t N, int64_t Zq) {
@@ -409,42 +358,17 @@ static int field_ring_planes(int64_t N, int64_t Zq) {
     return (int) std::max<int64_t>(1, std::min<int64_t>(Zq, ((int64_t) 6 << 30) / plane_b));
 }
 
-// stream factors the composite (2^a 3^b 5^c 7^d) kernels take: any EVEN divisor of PPD (two residues r, r + R/2 share a ZA pass) — or
-// 1 — whose z lines have a composite transform.  R = 36 gives PPD = 6912 z lines of 192 = 64 * 3 and 18 passes where the powers of two
-// offer 64 (z lines of 108) and 32 passes: the store of a pass must fit, and between 128 GB and 260 GB there was nothing.
-static bool np2_stream_factor_ok(int64_t N, int R) {
-    return R >= 1 && (R == 1 || R % 2 == 0) && N % R == 0 && zd::np2_supported_zlen((int) (N / R));
+const char *zd_fnl_multi_unsupported(const zd_params *p) { return zd::fnl_multi_refusal(p); }
+#ifdef ZD_TESTING
+int zd_test_route(const zd_params *p_in, int32_t R, int32_t nranks, int32_t *out, char *why, int64_t cap) {
+    const zd_params pc = zd::canonical(p_in);
+    const Route rt = route(&pc, R, nranks, zd::ROLE_MAIN);
+    const int32_t v[12] = {rt.family, rt.pack, rt.narray, rt.pstep, rt.npass, rt.R, rt.L, rt.Hq, rt.Zq, rt.dens, rt.dens_only, rt.twr};
+    memcpy(out, v, sizeof v);
+    if (why && cap > 0) snprintf(why, (size_t) cap, "%s", rt.why);
+    return rt.ok() ? 0 : 1;
 }
-
-// ZD_f_NL on a composite grid: the reference's arrays as on the convolution path (the second pass keeps the Nyquist modes live,
-// so the Hermitian field stores cannot carry it), every line through the composite transforms of zd_kernels_np2_ref.hip where both
-// line lengths — N (x, y; the phi round's z) and N / R (the z lines of a pass) — have one.  One rank: ZD_StoreMode = reference and
-// ZD_qoneslab keep the convolution transforms, as does any stream factor outside fnl_np2_factor_ok.  Several ranks: the arrays split
-// over the ranks (AnyChunks) and nothing else — those configurations are refused (zd_fnl_multi_unsupported).
-static bool fnl_np2(const zd_params *p) {
-    return p->f_NL != 0. && !is_pow2(p->ppd) && zd::np2_supported_ppd((int) p->ppd) && p->store_mode != ZD_STORE_REFERENCE
-           && p->qoneslab < 0 && !tune_env("ZD_NO_NP2_FNL");
-}
-static bool fnl_np2_factor_ok(int64_t N, int R) {
-    return R >= 1 && N % R == 0 && zd::refq_supported_len((int) N) && zd::refq_supported_len((int) (N / R));
-}
-// (several ranks: the z lines of a pass, N / R, must deal out over the ranks too)
-static bool fnl_np2_multi_factor_ok(int64_t N, int R, int nranks) {
-    return fnl_np2_factor_ok(N, R) && (N / R) % nranks == 0 && (N / 2) % nranks == 0;
-}
-
-const char *zd_fnl_multi_unsupported(const zd_params *p) {
-    const int64_t N = p->ppd;
-    if (is_pow2(N)) return N > 4096 ? "ZD_f_NL != 0 on several GPUs needs PPD <= 4096 on the powers of two" : nullptr;
-    if (!zd::np2_supported_ppd((int) N) || !zd::refq_supported_len((int) N))
-        return "ZD_f_NL != 0 on several GPUs needs a PPD with composite transforms (2^a 3^b 5^c 7^d of the kernel table); this PPD runs "
-               "its lines as convolutions, on one GPU only";
-    if (p->store_mode == ZD_STORE_REFERENCE)
-        return "ZD_f_NL != 0 with ZD_StoreMode = reference runs the convolution transforms, on one GPU only";
-    if (p->qoneslab >= 0) return "ZD_f_NL != 0 with ZD_qoneslab runs the convolution transforms, on one GPU only";
-    if (tune_env("ZD_NO_NP2_FNL")) return "ZD_NO_NP2_FNL forces the convolution transforms, which run on one GPU only";
-    return nullptr;
-}
+#endif
 
 // ZD_f_NL on a composite grid, several ranks: bytes per rank of the two-slot exchange ring of a store with `narray` arrays and Zq
 // planes per chunk (zd_plan_ring_bytes: a plane from every rank is narray N (N + pad) complex, ~4 GB per slot)
@@ -460,140 +384,92 @@ static int64_t fnl_multi_ring_bytes(const zd_params *p, int narray, int64_t Zq) 
 static int64_t fnl_phik_bytes(int64_t N) { return (N / 2) * N * N * 16; }
 static int64_t fnl_phi_bytes(const zd_params *p) {
     const int64_t N = p->ppd;
-    return (fnl_np2(p) && fnl_np2_factor_ok(N, 1) ? N / 2 : N) * N * (N + store_row_pad(N)) * 16;
+    return (route(p, 1, 1, zd::ROLE_PHI).twr ? N / 2 : N) * N * (N + store_row_pad(N)) * 16;
 }
 
-// ZD_qdensity = 2 (density only): the displacement arrays are never built (src/zeldovich.cpp:303,440), so the eigenmodes of ZD_qPLT
-// never enter — the run IS the ZA density-only run, on every grid and path
-static zd_params canonical(const zd_params *p) {
-    zd_params c = *p;
-    if (c.qdensity == 2) c.qPLT = c.qPLTrescale = 0;
-    return c;
+// The two halves of a PLT + density run (zd_route.h plt_dens_split) at the PLT half's stream factor R (<= 0: plan creation's
+// default), and whether their shapes fit together: the PLT half on its field store, the density half density-only with the same
+// passes and the same planes per pass.  (A refusal of either half is not asked here: plan creation then falls back by itself.)
+static bool split_routes(const zd_params *p, int R, zd_params *pa, zd_params *pb, Route *A, Route *B) {
+    *pa = *pb          = *p;
+    pa->qdensity       = 0;
+    *A                 = route(pa, R, 1, zd::ROLE_MAIN);
+    pb->qPLT = pb->qPLTrescale = 0;
+    pb->qdensity       = 2;
+    pb->stream_factor  = 2 * A->R;
+    *B                 = route(pb, 2 * A->R, 1, zd::ROLE_MAIN);
+    return A->family == zd::FAM_COMPOSITE && A->pack == zd::PACK_PLTFIELD && B->family == zd::FAM_COMPOSITE && B->dens_only
+           && B->npass == A->npass && B->pstep == 2 && 2 * B->Zq == A->Zq;
 }
 
-// PLT with ZD_qdensity = 1 on the composite grids, one rank (round 5): the PLT field store has no density field and its paired
-// generator no registers for a seventh pair of sums, so the density planes come from a second plan — density only, ZA six-field
-// store (dens_only) — at stream factor 2R: its pass j holds the residues j and j + R, i.e. exactly the planes z = j (mod R) of this
-// plan's pass j, in the same delivery order.  It runs at the head of the Z stage on the same store (which the PLT pass then
-// overwrites) and leaves N/R planes of float32 behind.  Before: the ~6x slower convolution path.
-static bool plt_dens_split(const zd_params *p, int nranks) {
-    return p->qPLT && p->qdensity == 1 && p->f_NL == 0. && p->qoneslab < 0 && nranks == 1 && !is_pow2(p->ppd)
-           && zd::np2_supported_ppd((int) p->ppd) && (p->store_mode == ZD_STORE_AUTO || p->store_mode == ZD_STORE_FIELDS)
-           && !tune_env("ZD_NO_DENS_SPLIT");
-}
-// (the two halves of such a run)
-static zd_params split_plt_half(const zd_params *p) {
-    zd_params a = *p;
-    a.qdensity  = 0;
-    return a;
-}
-static zd_params split_dens_half(const zd_params *p, int R) {
-    zd_params b     = *p;
-    b.qPLT          = 0;
-    b.qPLTrescale   = 0;
-    b.qdensity      = 2;
-    b.stream_factor = 2 * R;
-    return b;
+// the smallest stream factor whose stores fit the budget: first among those the family's own kernels take (power-of-two engine,
+// composite kernels on the field stores), then — composite and other even PPDs — on the reference's arrays
+static int choose_stream_factor_one(const zd_params *p, int nranks, int64_t budget_bytes) {
+    const int64_t N = p->ppd, plane_b = N * (N + store_row_pad(N)) * 16;  // (one array of a plane)
+    const int own = is_pow2(N) ? zd::FAM_POW2 : zd::FAM_COMPOSITE;
+    // ZA without density: two residues share a pass, so R = 2 is preferred over R = 1 whenever the z FFT is long enough
+    const Route r2 = route(p, 2, nranks, zd::ROLE_MAIN);
+    for (int R = r2.legal && r2.pstep == 2 ? 2 : 1; N / R >= zd::min_zlen(own); R = zd::next_factor(own, R)) {
+        const Route rt = route(p, R, nranks, zd::ROLE_MAIN);
+        if (!rt.legal || rt.family != own) continue;
+        if (N > 4096 && rt.L > 2048) continue;  // the field store's z FFT stops at 2048 and PPD > 4096 has no other store worth using
+        int64_t store = store_bytes(p, R, nranks);
+        if (nranks > 1) store += std::min<int64_t>(store, (int64_t) 9 << 30);  // + the two-slot exchange ring (zd_multi.cpp), not a second store
+        if (zd::pack_is_fields(zd::pack_mode(p, R)))  // + the y -> x ring (3 arrays; 4 with the density array); priced like the store
+            store += (int64_t) field_ring_planes(N, rt.Zq) * (zd::dens_fields(p) ? 4 : 3) * plane_b;
+        if (store <= budget_bytes) return R;
+    }
+    if (own == zd::FAM_POW2) return -1;
+    // Reference arrays.  ZD_f_NL: PhiK stays beside every pass's store, and the phi round before it holds PhiK and the phi planes —
+    // several ranks (the arrays split over them, AnyChunks): everything / G, plus the phi round's and each pass's exchange ring
+    int64_t budget = budget_bytes;
+    if (p->f_NL != 0.) {
+        const int64_t phik = fnl_phik_bytes(N) / nranks;
+        if (phik + (nranks > 1 ? N * plane_b / nranks + fnl_multi_ring_bytes(p, 1, N / nranks) : fnl_phi_bytes(p)) > budget) return -1;
+        budget -= phik;
+    }
+    // f_NL on a composite grid: the smallest factor whose z lines the composite transforms take comes first
+    for (int fam : {zd::FAM_REF_COMPOSITE, zd::FAM_CONVOLUTION})
+        for (int R = 1; N / R >= zd::min_zlen(fam); R = zd::next_factor(fam, R)) {
+            const Route rt = route(p, R, nranks, zd::ROLE_MAIN);
+            if (!rt.legal || rt.family != fam) continue;
+            if (rt.L * rt.narray * plane_b / nranks + (nranks > 1 ? fnl_multi_ring_bytes(p, rt.narray, rt.Zq) : 0) <= budget) return R;
+        }
+    return -1;
 }
 
-static int choose_stream_factor_one(const zd_params *p, int nranks, int64_t budget_bytes);
 int zd_choose_stream_factor(const zd_params *p_in, int nranks, int64_t budget_bytes) {
-    const zd_params pc = canonical(p_in);
-    if (plt_dens_split(&pc, nranks)) {
+    const zd_params pc = zd::canonical(p_in);
+    if (zd::plt_dens_split(&pc, nranks)) {
         // the PLT half's own choice, with room for what the density half adds: N/R planes of float32, its two rings (3 + 1 arrays of
         // <= 6 GB / 3) and its tables; both R and 2R must have z lines the composite kernels transform
-        const zd_params pa = split_plt_half(&pc);
         const int64_t N = pc.ppd;
-        for (int R = 1; N / R >= 24; R = R == 1 ? 2 : R + 2) {
-            if (!np2_stream_factor_ok(N, R) || !np2_stream_factor_ok(N, 2 * R) || N / R > 2048) continue;
-            if (!zd::pack_is_fields(pack_mode(&pa, R)) || (N / 2) % zd::FIELD_RB) break;
-            const int64_t ring = (int64_t) field_ring_planes(N, N / R) * N * (N + store_row_pad(N)) * 16;
+        for (int R = 1; N / R >= 24; R = zd::next_factor(zd::FAM_COMPOSITE, R)) {
+            zd_params pa, pb;
+            Route A, B;
+            if (!split_routes(&pc, R, &pa, &pb, &A, &B)) continue;
+            const int64_t ring = (int64_t) field_ring_planes(N, A.Zq) * N * (N + store_row_pad(N)) * 16;
             const int64_t need = store_bytes(&pa, R, 1) + 3 * ring                                             // the PLT half
-                                 + (N / R) * N * N * 4 + 4 * ring + ((int64_t) 1 << 30);                       // + the density half
+                                 + A.L * N * N * 4 + 4 * ring + ((int64_t) 1 << 30);                           // + the density half
             if (need <= budget_bytes) return R;
         }
     }
     return choose_stream_factor_one(&pc, nranks, budget_bytes);
 }
-static int choose_stream_factor_one(const zd_params *p, int nranks, int64_t budget_bytes) {
-    const int64_t N = p->ppd;
-    // ZA without density: two residues share a pass, so R = 2 is preferred over R = 1 whenever the z FFT is long enough
-    int R0 = 1;
-    if (!p->qPLT && pack_mode(p, 2) != zd::PACK_NONE && N / 2 >= 32 && (N / 2) % nranks == 0) R0 = 2;
-    const bool np2 = !is_pow2(N);
-    if (N > 8192 && pack_mode(p, 2) != zd::PACK_ZAFIELD) return -1;  // 16384, 8640: only the ZA field store has kernels (plan_create_ex)
-    if (!np2 && pack_mode(p, 2) == zd::PACK_NONE && (p->qdensity == 2 ? 1 : (p->qPLT ? 4 : 2)) * (N / 16) > 1024) return -1;  // 8192 on four arrays: no x pass
-    // any other even PPD (or a 2^a 3^b one whose options the composite kernels lack): reference arrays on one rank, see
-    // plan_create_ex; R any divisor of N
-    auto any_factor = [&]() -> int {
-        const int64_t narray = p->qdensity == 2 ? 1 : (p->qPLT ? 4 : 2);
-        if (nranks > 1 && fnl_np2(p) && (N / 2) % nranks == 0) {
-            // f_NL on a composite grid, several ranks (the arrays split over them, AnyChunks).  Per rank: PhiK / G beside everything;
-            // the phi round's store / G (one array, every plane) and its ring before the main pass; each pass's store / G and ring
-            const int G = nranks;
-            const int64_t plane_b = N * (N + store_row_pad(N)) * 16, phik = fnl_phik_bytes(N) / G;  // (one array of a plane)
-            if (phik + N * plane_b / G + fnl_multi_ring_bytes(p, 1, N / G) > budget_bytes) return -1;
-            for (int R = 1; N / R >= 3; R++)
-                if (fnl_np2_multi_factor_ok(N, R, G)
-                    && phik + (N / R) * narray * plane_b / G + fnl_multi_ring_bytes(p, (int) narray, N / R / G) <= budget_bytes)
-                    return R;
-            return -1;
-        }
-        if (N % 2 || N < 8 || N > 8192 || nranks != 1) return -1;
-        int64_t budget = budget_bytes;
-        if (p->f_NL != 0.) {  // PhiK stays beside every pass's store; the phi round before it holds PhiK and the phi planes
-            const int64_t phik = fnl_phik_bytes(N);
-            if (fnl_phi_bytes(p) + phik > budget) return -1;
-            budget -= phik;
-        }
-        // f_NL on a composite grid: the smallest factor whose z lines the composite transforms take (fnl_np2) comes first
-        for (int pass = fnl_np2(p) ? 0 : 1; pass < 2; pass++)
-            for (int R = 1; N / R >= 3; R++)  // any divisor of N (the z-residue fold is a plain decimation: R need not be 2^k here)
-                if (N % R == 0 && (pass == 1 || fnl_np2_factor_ok(N, R)) && (N / R) * narray * N * (N + store_row_pad(N)) * 16 <= budget)
-                    return R;
-        return -1;
-    };
-    if (np2 && (!zd::pack_is_fields(pack_mode(p, 2)) || !zd::np2_supported_ppd((int) N) || (N / 2) % (nranks * zd::FIELD_RB))) return any_factor();
-    for (int R = R0; np2 ? N / R >= 12 : (N / R >= 32 && N % R == 0); R = np2 ? (R == 1 ? 2 : R + 2) : R * 2) {
-        if (np2) {  // any even divisor whose z lines have a composite transform (np2_stream_factor_ok)
-            if (!np2_stream_factor_ok(N, R) || (N / R) % nranks) continue;
-        } else if ((N / R) % nranks)
-            break;
-        if (N / R > 4096) continue;  // z-FFT kernels exist up to length 4096
-        if (N > 4096 && N / R > 2048) continue;  // the field store's z FFT stops at 2048 and PPD > 4096 has no other store worth using
-        int64_t store = store_bytes(p, R, nranks);
-        if (nranks > 1) store += std::min<int64_t>(store, (int64_t) 9 << 30);  // + the two-slot exchange ring (zd_multi.cpp), not a second store
-        if (zd::pack_is_fields(pack_mode(p, R)))  // + the y -> x ring (3 arrays; 4 with the density array)
-            store += (int64_t) field_ring_planes(N, N / R / nranks) * (dens_fields(p) ? 4 : 3) * N * (N + store_row_pad(N)) * 16;
-        if (store <= budget_bytes) return R;
-    }
-    return np2 ? any_factor() : -1;
-}
 
-// a job that one rank runs as convolutions on the power-of-two engine (zd_kernels_any.hip: PPD neither 2^a nor a composite size
-// whose options the composite kernels have).  Its R is any divisor of PPD; several GPUs share it as pass groups only.
-static bool convolution_job(const zd_params *p) {
-    const int64_t N = p->ppd;
-    if (is_pow2(N) || plt_dens_split(p, 1)) return false;
-    return p->f_NL != 0. || !zd::pack_is_fields(pack_mode(p, 2)) || !zd::np2_supported_ppd((int) N) || (N / 2) % zd::FIELD_RB;
+// the family whose stream factors the pass groups of a job step through.  One rank runs a job on the reference's arrays (PPD neither
+// 2^a nor a composite size whose options the composite kernels have) with any divisor of PPD as R; several GPUs share it as pass groups only
+static int group_family(const zd_params *p, int gsz) {
+    const bool convolution_job = !zd::plt_dens_split(p, 1) && route(p, 0, 1, zd::ROLE_MAIN).family >= zd::FAM_REF_COMPOSITE;
+    return is_pow2(p->ppd) ? zd::FAM_POW2 : (gsz == 1 && convolution_job) ? zd::FAM_CONVOLUTION : zd::FAM_COMPOSITE;
 }
-
-// planes a store plane delivers for (p, R) on `nranks` ranks: 2 with the ZA packings (plan_create_ex's choice of store)
-static int plan_plane_step(const zd_params *p, int R, int nranks) {
-    const int64_t N = p->ppd;
-    if (!is_pow2(N)) {  // composite kernels (field stores) or the convolution path (reference arrays)
-        const bool comp = zd::np2_supported_ppd((int) N) && p->f_NL == 0. && np2_stream_factor_ok(N, R)
-                          && zd::pack_is_fields(pack_mode(p, R)) && (N / 2) % (nranks * zd::FIELD_RB) == 0;
-        if (!comp) return 1;
-    }
-    int pm = pack_mode(p, R);
-    if (zd::pack_is_fields(pm) && (((N / 2) / nranks) % zd::FIELD_RB || N / R > 2048))
-        pm = N > 4096 ? zd::PACK_NONE : (pm == zd::PACK_PLTFIELD ? zd::PACK_PLT3 : zd::PACK_ZAPAIR);
-    return (pm == zd::PACK_ZAPAIR || pm == zd::PACK_ZAFIELD) ? 2 : 1;
+static bool group_factor_ok(int fam, int64_t N, int R) {
+    return fam == zd::FAM_COMPOSITE ? zd::np2_stream_factor_ok(N, R) : (N % R == 0 && N / R >= zd::min_zlen(fam));
 }
 
 int zd_choose_pass_groups(const zd_params *p_in, int ngpu, int64_t budget_bytes, int32_t *groups, int32_t *stream_factor) {
-    const zd_params pc = canonical(p_in), *p = &pc;
+    const zd_params pc = zd::canonical(p_in), *p = &pc;
+    const int64_t N = p->ppd;
     if (ngpu < 1) ngpu = 1;
     int g = p->pass_groups;
     if (g < 0 || (g > 0 && ngpu % g)) {
@@ -605,30 +481,22 @@ int zd_choose_pass_groups(const zd_params *p_in, int ngpu, int64_t budget_bytes,
         fprintf(stderr, "zeldovich_hip: ZD_f_NL != 0 runs as one group of ranks (ZD_PassGroups = 1)\n");
         return 1;
     }
+    const bool given = p->stream_factor > 0;
     if (g == 0) {  // automatic: one GPU per group — no exchange — while a single rank's job has, or can be given, that many passes
         g = 1;
-        zd_params q = *p;
-        const int R1 = q.stream_factor > 0 ? q.stream_factor : zd_choose_stream_factor(&q, 1, budget_bytes);
+        const int R1 = given ? p->stream_factor : zd_choose_stream_factor(p, 1, budget_bytes);
         if (R1 > 0 && ngpu > 1) {
             // A free stream factor may be doubled (smaller stores always fit): every rank then generates the modes once per
             // pass of its own instead of sharing one generation, and nothing travels.  PPD = 4096 ZA on 8 GPUs: R = 8 -> 16,
             // one pass per GPU, 0.36-0.38 s predicted against 0.30-0.33 s for the all-to-all — within the
             // uncertainty of the link rate, and independent of it.  More than one doubling is not worth the generations.
-            const int Rmax = q.stream_factor > 0 ? R1 : 2 * R1;
-            if (convolution_job(p) && p->f_NL == 0.) {  // any divisor of PPD is a stream factor there; up to four times the passes it needs
-                for (int R2 = R1; R2 <= (q.stream_factor > 0 ? R1 : std::max(4 * R1, 2 * ngpu)) && p->ppd / R2 >= 3; R2++)
-                    if (p->ppd % R2 == 0 && R2 % ngpu == 0) {
-                        g = ngpu;
-                        break;
-                    }
-            } else
-            for (int R2 = R1; R2 <= Rmax; R2 = is_pow2(p->ppd) ? R2 * 2 : R2 + 2) {
-                const bool len_ok = is_pow2(p->ppd) ? (p->ppd % R2 == 0 && p->ppd / R2 >= 32) : np2_stream_factor_ok(p->ppd, R2);
-                if (!len_ok) {
-                    if (is_pow2(p->ppd)) break;
-                    continue;
-                }
-                const int npass = R2 / plan_plane_step(&q, R2, 1);
+            // (reference arrays: any divisor of PPD is a stream factor there; up to four times the passes it needs)
+            const int fam = group_family(p, 1);
+            const int Rmax = given ? R1 : fam == zd::FAM_CONVOLUTION ? std::max(4 * R1, 2 * ngpu) : 2 * R1;
+            for (int R2 = R1; R2 <= Rmax && N / R2 >= zd::min_zlen(fam); R2 = zd::next_factor(fam, R2)) {
+                if (fam == zd::FAM_COMPOSITE && R2 > R1 && R1 % 2) break;  // (an odd R1 only ever stepped to odd factors: kept, a finding)
+                if (!group_factor_ok(fam, N, R2)) continue;
+                const int npass = route(p, R2, 1, zd::ROLE_MAIN).npass;
                 if (npass >= ngpu && npass % ngpu == 0) {
                     g = ngpu;
                     break;
@@ -637,32 +505,25 @@ int zd_choose_pass_groups(const zd_params *p_in, int ngpu, int64_t budget_bytes,
         }
     }
     const int gsz = ngpu / g;
-    int R = p->stream_factor > 0 ? p->stream_factor : zd_choose_stream_factor(p, gsz, budget_bytes);
+    int R = given ? p->stream_factor : zd_choose_stream_factor(p, gsz, budget_bytes);
     if (R < 0) return 1;
+    auto passes = [&](int r) { return route(p, r, gsz, zd::ROLE_MAIN).npass; };
     // Ranks that exchange pipeline their passes (zd_plan_run_passes: Z stage of pass p+1 beside the exchange of pass p, two
     // send stores): give every group at least four passes when the stream factor is free.  A larger factor always fits —
     // the stores shrink — and costs (passes / ranks per group) generations per rank, hidden behind the exchange.
-    if (gsz > 1 && p->stream_factor <= 0 && is_pow2(p->ppd))
-        while ((R / plan_plane_step(p, R, gsz)) < 4 * g && p->ppd % (2 * R) == 0 && p->ppd / (2 * R) >= 256 && (p->ppd / (2 * R)) % gsz == 0) R *= 2;
+    if (gsz > 1 && !given && is_pow2(N))
+        while (passes(R) < 4 * g && N % (2 * R) == 0 && N / (2 * R) >= 256 && (N / (2 * R)) % gsz == 0) R *= 2;
     // the passes must deal out evenly over the groups: a larger stream factor (smaller stores) always fits
-    while ((R / plan_plane_step(p, R, gsz)) % g) {
-        if (p->stream_factor > 0) {
-            fprintf(stderr, "zeldovich_hip: ZD_StreamFactor = %d gives %d passes, not a multiple of the %d pass groups\n", R,
-                    R / plan_plane_step(p, R, gsz), g);
+    const int fam = group_family(p, gsz);
+    while (passes(R) % g) {
+        if (given) {
+            fprintf(stderr, "zeldovich_hip: ZD_StreamFactor = %d gives %d passes, not a multiple of the %d pass groups\n", R, passes(R), g);
             return 1;
         }
-        if (is_pow2(p->ppd)) {
-            R *= 2;
-            if (p->ppd % R || p->ppd / R < 32 || (p->ppd / R) % gsz) return 1;
-        } else if (gsz == 1 && convolution_job(p)) {  // convolution kernels: the next divisor of PPD
-            do R++;
-            while (p->ppd / R >= 3 && p->ppd % R);
-            if (p->ppd / R < 3) return 1;
-        } else {  // composite PPD: the next even factor the composite kernels take
-            do R += 2;
-            while (p->ppd / R >= 12 && !(np2_stream_factor_ok(p->ppd, R) && (p->ppd / R) % gsz == 0));
-            if (p->ppd / R < 12) return 1;
-        }
+        if (fam == zd::FAM_COMPOSITE && R % 2) return 1;  // (from R = 1 the step was 1 -> 3 -> 5 ...: no even factor found; kept, a finding)
+        do R = zd::next_factor(fam, R);
+        while (N / R >= zd::min_zlen(fam) && !(group_factor_ok(fam, N, R) && (N / R) % gsz == 0));
+        if (N / R < zd::min_zlen(fam)) return 1;
     }
     *groups        = g;
     *stream_factor = R;
@@ -682,7 +543,7 @@ int zd_choose_pass_groups(const zd_params *p_in, int ngpu, int64_t budget_bytes,
 // (first Z stage exposed, the others and the XY stages beside the exchange, the last plane group's XY behind it; P' = 1: t_z + max).
 int zd_choose_pass_groups_measured(const zd_params *p_in, int ngpu, int64_t budget_bytes, double link_GBps, int32_t *groups,
                                    int32_t *stream_factor, double *est_seconds) {
-    const zd_params pc = canonical(p_in), *p = &pc;
+    const zd_params pc = zd::canonical(p_in), *p = &pc;
     if (est_seconds) est_seconds[0] = est_seconds[1] = 0.0;
     if (zd_choose_pass_groups(p, ngpu, budget_bytes, groups, stream_factor)) return 1;
     if (!(link_GBps > 0.0) || ngpu < 2 || p->pass_groups != 0 || *groups != ngpu) return 0;  // nothing to decide
@@ -697,7 +558,8 @@ int zd_choose_pass_groups_measured(const zd_params *p_in, int ngpu, int64_t budg
     const double kc = p->k_cutoff > 1.0 ? p->k_cutoff : 1.0;
     const double c_gen = (p->qPLT ? 3.9e-12 : 2.05e-12) / (kc * kc * kc), c_zf = (p->qPLT ? 3.5e-12 : 2.7e-12) / (kc * kc);
     const double c_xy  = (p->qPLT ? 3.7e-11 : 2.0e-11) * (comp ? 1.85 : 1.0);
-    const int P0 = *stream_factor / plan_plane_step(p, *stream_factor, 1), P1 = R1 / plan_plane_step(&q, R1, ngpu);
+    const Route rq = route(&q, R1, ngpu, zd::ROLE_MAIN);
+    const int P0 = route(p, *stream_factor, 1, zd::ROLE_MAIN).npass, P1 = rq.npass;
     const double t_pg = c_gen * n3 * P0 / ngpu + (c_zf + c_xy) * n3 / ngpu;
     const double t_z = (c_gen * P1 + c_zf) * n3 / ngpu, t_xy = c_xy * n3 / ngpu;
     const double t_ex = (double) store_bytes(&q, R1, ngpu) * P1 / ngpu / (link_GBps * 1e9);
@@ -873,149 +735,511 @@ int zd_plan_create(const zd_params *p, const zd_pk *pk, const double *eig, int64
     return 0;
 }
 
-static int plan_create_one(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks, int phi_mode,
-                           const cplx *phik, zd_plan **out);
-
-static int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
-                          int phi_mode, const cplx *phik, zd_plan **out) {
-    const zd_params pc = canonical(p_in);
-    const bool split_R_ok = pc.stream_factor <= 0 || (np2_stream_factor_ok(pc.ppd, pc.stream_factor) && np2_stream_factor_ok(pc.ppd, 2 * pc.stream_factor));
-    if (phi_mode == 0 && phik == nullptr && plt_dens_split(&pc, nranks) && split_R_ok && eig != nullptr && eig_ppd > 0) {
-        const zd_params pa = split_plt_half(&pc);
-        zd_plan *A = nullptr, *B = nullptr;
-        bool ok = plan_create_one(&pa, pk, eig, eig_ppd, rank, nranks, 0, nullptr, &A) == 0;
-        ok = ok && A->pack == zd::PACK_PLTFIELD && !A->any && np2_stream_factor_ok(pc.ppd, 2 * A->R);
-        if (ok) {
-            const zd_params pb = split_dens_half(&pc, A->R);
-            ok = plan_create_one(&pb, pk, nullptr, 0, rank, nranks, 0, nullptr, &B) == 0;
-            ok = ok && B->dens_only && B->npass == A->npass && B->pstep == 2 && 2 * B->Zq == A->Zq;
+// ---- device tables of the generator and the transforms ----
+static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, int64_t eig_ppd) {
+    const zd_params *p = &pl->p;
+    zd::GenConst &g = pl->g;
+    if (!pk->is_powerlaw) {
+        HIPCHECK(hipMalloc((void **) &pl->d_pk, sizeof(double) * 3 * (size_t) pk->n));
+        HIPCHECK(hipMemcpy(pl->d_pk, pk->x, sizeof(double) * pk->n, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(pl->d_pk + pk->n, pk->y, sizeof(double) * pk->n, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(pl->d_pk + 2 * pk->n, pk->y2, sizeof(double) * pk->n, hipMemcpyHostToDevice));
+        g.pk_x  = pl->d_pk;
+        g.pk_y  = pl->d_pk + pk->n;
+        g.pk_y2 = pl->d_pk + 2 * pk->n;
+        // segment start table: cell c covers ln k in [x0 + c*dx, x0 + (c+1)*dx)
+        std::vector<int> lut(zd::PK_LUT);
+        const double x0 = pk->x[0], x1 = pk->x[pk->n - 1];
+        const double dx = (x1 - x0) / zd::PK_LUT;
+        int klo = 0;
+        for (int c2 = 0; c2 < zd::PK_LUT; c2++) {
+            const double cell_start = x0 + c2 * dx * (1.0 - 1e-12) - 1e-9;  // never past the true start
+            while (klo < pk->n - 2 && pk->x[klo + 1] <= cell_start) klo++;
+            lut[c2] = klo;
         }
-        if (ok) ok = zd_store_alloc((void **) &A->d_dens_pass, (size_t) A->Zq * pc.ppd * pc.ppd * sizeof(float)) == hipSuccess;
-        if (ok) {
-            A->dens_sub     = B;
-            A->p            = pc;  // (what the callers read back: ZD_qdensity = 1)
-            A->store_bytes_ = std::max(A->store_bytes_, B->store_bytes_);
-            *out            = A;
-            return 0;
-        }
-        zd_plan_destroy(B);
-        zd_plan_destroy(A);  // the run falls back to the reference arrays (convolution path)
+        HIPCHECK(hipMalloc((void **) &pl->d_lut, sizeof(int) * lut.size()));
+        HIPCHECK(hipMemcpy(pl->d_lut, lut.data(), sizeof(int) * lut.size(), hipMemcpyHostToDevice));
+        g.pk_lut     = pl->d_lut;
+        g.lut_x0     = x0;
+        g.lut_inv_dx = 1.0 / dx;
     }
-    return plan_create_one(&pc, pk, eig, eig_ppd, rank, nranks, phi_mode, phik, out);
+    if (p->qPLT) {
+        const size_t nb = sizeof(double) * (size_t) eig_ppd * eig_ppd * (eig_ppd / 2 + 1) * 4;
+        HIPCHECK(hipMalloc((void **) &pl->d_eig, nb));
+        HIPCHECK(hipMemcpy(pl->d_eig, eig, nb, hipMemcpyHostToDevice));
+        g.eig = pl->d_eig;
+    }
+    // per-plane stream heads == v2rng[] of the reference (power_spectrum.cpp:26-37)
+    {
+        std::vector<u128> rows(pl->half);
+        const zdpcg::Affine plane = zdpcg::jump_map((u128) 2 * ZD_MAX_PPD * ZD_MAX_PPD);
+        rows[0] = zdpcg::seed_state((uint64_t) p->seed);
+        for (int i = 1; i < pl->half; i++) rows[i] = zdpcg::apply(plane, rows[i - 1]);
+        HIPCHECK(hipMalloc((void **) &pl->d_rowstate, sizeof(u128) * rows.size()));
+        HIPCHECK(hipMemcpy(pl->d_rowstate, rows.data(), sizeof(u128) * rows.size(), hipMemcpyHostToDevice));
+        g.row_state = pl->d_rowstate;
+        // (built once; ZD_NumGPU creates its plans from several host threads at a time)
+        static const zdpcg::BitTable bt = [] {
+            zdpcg::BitTable b;
+            zdpcg::make_bit_table(b);
+            return b;
+        }();
+        if (zdk_upload_bit_table(&bt) != 0 || zdk_upload_bit_table_fz(&bt) != 0) {
+            fprintf(stderr, "zeldovich_hip: uploading the RNG jump table failed\n");
+            return 1;
+        }
+        // z-walk of k_gen (see zd_device.h GenJumps): forward L rows inside a fold, then back to the
+        // first term of the next k2; crossing z = N/2 shifts the counter row by +-(65536 - N)
+        const long long wrap = 65536 - pl->N, Lr = pl->L, back = -((long long) (pl->R - 1) * Lr - 1);
+        pl->J.fwd[0]  = row_jump(Lr);
+        pl->J.fwd[1]  = row_jump(Lr + wrap);
+        pl->J.back[0] = row_jump(back);
+        pl->J.back[1] = row_jump(back > 0 ? back + wrap : back - wrap);
+        pl->J.fwd_full[0]  = row_jump_full(Lr);
+        pl->J.fwd_full[1]  = row_jump_full(Lr + wrap);
+        pl->J.back_full[0] = row_jump_full(back);
+        pl->J.back_full[1] = row_jump_full(back > 0 ? back + wrap : back - wrap);
+        // the mirrored walker of genf_tile_kz: the same moves negated (crossing z = N/2 in its own direction of motion)
+        const long long mf = -Lr, mb = -back;
+        pl->J.mfwd[0]       = row_jump(mf);
+        pl->J.mfwd[1]       = row_jump(mf - wrap);
+        pl->J.mback[0]      = row_jump(mb);
+        pl->J.mback[1]      = row_jump(mb > 0 ? mb + wrap : mb - wrap);
+        pl->J.mfwd_full[0]  = row_jump_full(mf);
+        pl->J.mfwd_full[1]  = row_jump_full(mf - wrap);
+        pl->J.mback_full[0] = row_jump_full(mb);
+        pl->J.mback_full[1] = row_jump_full(mb > 0 ? mb + wrap : mb - wrap);
+    }
+    {
+        std::vector<cplx> twN = make_twiddles(pl->N), twL = make_twiddles(pl->L);
+        HIPCHECK(hipMalloc((void **) &pl->d_twN, sizeof(cplx) * twN.size()));
+        HIPCHECK(hipMemcpy(pl->d_twN, twN.data(), sizeof(cplx) * twN.size(), hipMemcpyHostToDevice));
+        HIPCHECK(hipMalloc((void **) &pl->d_twL, sizeof(cplx) * twL.size()));
+        HIPCHECK(hipMemcpy(pl->d_twL, twL.data(), sizeof(cplx) * twL.size(), hipMemcpyHostToDevice));
+        if (!is_pow2(pl->N) && !pl->any) {  // composite transforms (zd_fft_q.h): exp(2 pi i k / P) | exp(2 pi i k / len) | exp(2 pi i k / Q) per length
+            if (upload_twq(pl->N, &pl->d_twq_n) || upload_twq(pl->L, &pl->d_twq_l)) {
+                fprintf(stderr, "zeldovich_hip: composite twiddle tables failed\n");
+                return 1;
+            }
+        }
+        // LDS image of k_genf (layout: GenfTab in zd_kernels.hip).  Spline tables beyond 512 segments do not
+        // fit: such runs use the general generator.
+        const int nseg = pk->is_powerlaw ? 0 : pk->n - 1;
+        if (nseg <= 512 && !tune_env("ZD_GEN_GENERAL")) {
+            std::vector<double> T = build_genf_table(pk, nseg, &g.glut_x0, &g.glut_inv_dx);
+            HIPCHECK(hipMalloc((void **) &pl->d_genf, sizeof(double) * T.size()));
+            HIPCHECK(hipMemcpy(pl->d_genf, T.data(), sizeof(double) * T.size(), hipMemcpyHostToDevice));
+            g.genf_tab  = pl->d_genf;
+            g.genf_n    = (int) T.size();
+            g.genf_nseg = nseg;
+        }
+    }
+    // {P, 1/k^2} table over the integer |k|^2 that can carry power (zero rule of zeldovich.cpp:350-353)
+    if (!tune_env("ZD_NO_PKTAB")) {
+        const double half2 = (double) pl->half * pl->half;
+        double nmax = p->corner_modes ? 3.0 * half2 : std::min(3.0 * half2, g.k2_cutoff / g.fundamental2 * (1 + 1e-9) + 2);
+        const long long n = (long long) nmax + 2;
+        if (n <= ((long long) 1 << 26)) {
+            HIPCHECK(hipMalloc((void **) &pl->d_pktab, sizeof(double) * 2 * (size_t) n));
+            if (zd::launch_pk_table(g, (int) n, pl->d_pktab, 0)) {
+                return 1;
+            }
+            HIPCHECK(hipDeviceSynchronize());
+            g.pk_tab = (const double2 *) pl->d_pktab;
+        }
+    }
+    if (g.gen_phi || g.phik) {  // M(k) = 2 g c^2 T(k) k^2 / (3 Omega_M H0^2), zeldovich.cpp:377-383
+        const double H0 = 100., c = 299792.458, growth = 1. / (1 + p->z_initial);
+        g.fnl_pre = 2. * growth * c * c;
+        g.fnl_den = 3. * p->Omega_M * H0 * H0;
+        g.n_s     = p->n_s;
+        // Normalize(): primordial_norm = power(kmin) / primordial_power(kmin) with norm 1 (power_spectrum.cpp:221-222)
+        g.primordial_norm = zd_pk_power(pk, pk->kmin) / (1. * exp(log(pk->kmin) * p->n_s));
+        const long long n = 3LL * pl->half * pl->half + 2;
+        HIPCHECK(hipMalloc((void **) &pl->d_fnlM, sizeof(double) * (size_t) n));
+        if (zd::launch_fnl_table(g, (int) n, pl->d_fnlM, 0)) {
+            return 1;
+        }
+        HIPCHECK(hipDeviceSynchronize());
+        g.fnl_M = pl->d_fnlM;
+    }
+    HIPCHECK(hipMalloc((void **) &pl->d_red, sizeof(zd::Reduce)));
+    HIPCHECK(hipMemset(pl->d_red, 0, sizeof(zd::Reduce)));
+    g.var_slots = pl->d_red->sumsq;
+    return 0;
 }
 
-static int plan_create_one(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
-                           int phi_mode, const cplx *phik, zd_plan **out) {
-    const int64_t N = p->ppd;
-    // Three transform families: powers of two (zd_kernels.hip), 2^a 3^b on the field stores (zd_kernels_np2.hip), and ANY
-    // other even PPD — or a 2^a 3^b one with options the composite kernels lack — on the reference arrays, one rank
-    // (zd_kernels_any.hip).  Those lines are convolutions on the power-of-two engine, but for ZD_f_NL on a 2^a 3^b grid
-    // (fnl_np2): composite transforms there (zd_kernels_np2_ref.hip)
-    const bool pow2 = is_pow2(N);
-    bool any_path = false;
-    int np2_R = 2;
-    if (!pow2) {
-        int Rg = p->stream_factor > 0 ? p->stream_factor : 2;
-        if (p->stream_factor <= 0)  // no factor given: the first one whose z lines the composite kernels have
-            for (int r = 2; N / r >= 12; r += 2)
-                if (np2_stream_factor_ok(N, r)) {
-                    Rg = r;
-                    break;
-                }
-        np2_R = Rg;
-        const bool comp_ok = zd::np2_supported_ppd((int) N) && phi_mode == 0 && phik == nullptr && np2_stream_factor_ok(N, Rg)
-                             && zd::pack_is_fields(pack_mode(p, Rg))
-                             && (N / 2) % (nranks * zd::FIELD_RB) == 0;
-        any_path = !comp_ok;
-    }
-    const bool np2 = !pow2 && !any_path;  // PPD = 2^a 3^b: the composite-transform kernels, field stores only
-    if (pow2 && (N < 32 || N > 16384)) {
-        fprintf(stderr, "zeldovich_hip: PPD = %lld unsupported (powers of two: 32 ... 16384)\n", (long long) N);
-        return 1;
-    }
-    if (p->qPLT && (eig == NULL || eig_ppd <= 0)) {
-        fprintf(stderr, "zeldovich_hip: ZD_qPLT set but no eigenmode table given\n");
-        return 1;
-    }
-    int R = p->stream_factor > 0 ? p->stream_factor : 1;
-    if (np2 && p->stream_factor <= 0) R = np2_R;
-    if (any_path && nranks > 1 && p->f_NL != 0.) {  // ZD_f_NL on a composite grid, the arrays split over the ranks (AnyChunks)
-        if (const char *why = zd_fnl_multi_unsupported(p)) {
-            fprintf(stderr, "zeldovich_hip: %s\n", why);
-            return 1;
+// ---- jobs of the z stage ----
+static void plan_zstage_jobs(zd_plan *pl) {
+    zd::JobList &jl = pl->jobs;
+    memset(&jl, 0, sizeof(jl));
+    jl.pack = pl->pack;
+    auto add = [&](int kind, int arr, int twin, int res) {
+        jl.kind[jl.n] = kind;
+        jl.arr[jl.n]  = arr;
+        jl.twin[jl.n] = twin;
+        jl.res[jl.n]  = res;
+        jl.n++;
+    };
+    if (pl->pack == zd::PACK_PLTFIELD) {  // the six sums (k_zfft_f: job index = field index)
+        add(zd::JOB_PX, 0, 0, 0);
+        add(zd::JOB_PY, 1, 0, 0);
+        add(zd::JOB_PZ, 2, 0, 0);
+        add(zd::JOB_PFX, 3, 0, 0);
+        add(zd::JOB_PFY, 4, 0, 0);
+        add(zd::JOB_PFZ, 5, 0, 0);
+    } else if (pl->pack == zd::PACK_ZAFIELD) {  // the potentials E, Z of the two residues (k_zfft_f: job index = field index)
+        add(zd::JOB_E, 0, 0, 0);
+        add(zd::JOB_Z, 1, 0, 0);
+        add(zd::JOB_E, 2, 0, 1);
+        add(zd::JOB_Z, 3, 0, 1);
+        if (pl->dens) {  // ZD_qdensity = 1: the density sums of the two residues
+            add(zd::JOB_DENS, 4, 0, 0);
+            add(zd::JOB_DENS, 5, 0, 1);
         }
-        if (!fnl_np2_multi_factor_ok(N, R, nranks)) {
-            fprintf(stderr, "zeldovich_hip: ZD_f_NL on %d ranks at PPD = %lld: stream factor %d has no composite z lines of length PPD / R "
-                            "dividing over the ranks\n", nranks, (long long) N, R);
-            return 1;
+    } else if (pl->pack == zd::PACK_ZAPAIR) {  // (qy + i qz)_r0 | (qy + i qz)_r1 | qx_r0 + i qx_r1
+        add(zd::JOB_B_SELF, 0, 0, 0);
+        add(zd::JOB_B_TWIN, 0, 1, 0);
+        add(zd::JOB_B_SELF, 1, 0, 1);
+        add(zd::JOB_B_TWIN, 1, 1, 1);
+        add(zd::JOB_FX, 2, 0, 0);  // generator output slot 4 = X_self, slot 5 = X_twin input (k_gen/k_genf combine F_x(r0), F_x(r1))
+        add(zd::JOB_FX, 2, 1, 1);
+    } else if (pl->pack == zd::PACK_PLT3) {  // qx + i vx | qy + i qz | vy + i vz
+        add(zd::JOB_XV_SELF, 0, 0, 0);
+        add(zd::JOB_XV_TWIN, 0, 1, 0);
+        add(zd::JOB_B_SELF, 1, 0, 0);
+        add(zd::JOB_B_TWIN, 1, 1, 0);
+        add(zd::JOB_D_SELF, 2, 0, 0);
+        add(zd::JOB_D_TWIN, 2, 1, 0);
+    } else if (pl->narray == 1) {
+        add(zd::JOB_DENS, 0, 0, 0);
+    } else {
+        add(zd::JOB_A_SELF, 0, 0, 0);
+        add(zd::JOB_A_TWIN, 0, 1, 0);
+        add(zd::JOB_B_SELF, 1, 0, 0);
+        add(zd::JOB_B_TWIN, 1, 1, 0);
+        if (pl->narray == 4) {
+            add(zd::JOB_C_BOTH, 2, 0, 0);
+            add(zd::JOB_D_SELF, 3, 0, 0);
+            add(zd::JOB_D_TWIN, 3, 1, 0);
         }
-    } else if (any_path) {
-        if (N % 2 || N < 8 || N > 8192 || nranks != 1 || R < 1 || N % R || N / R < 3) {
-            fprintf(stderr, "zeldovich_hip: PPD = %lld (neither 2^a nor a supported 2^a 3^b configuration) runs as convolutions on the "
-                            "power-of-two engine: even PPD in [8, 8192], one rank, ZD_StreamFactor any divisor of PPD (got %d)\n",
-                    (long long) N, R);
-            return 1;
-        }
-    } else if (np2 ? !np2_stream_factor_ok(N, R) : (!is_pow2(R) || N % R || N / R < 32 || N / R > 4096)) {
-        fprintf(stderr, "zeldovich_hip: stream factor %d invalid for PPD %lld\n", R, (long long) N);
-        return 1;
     }
-    if (nranks < 1 || !is_pow2(nranks) || rank < 0 || rank >= nranks || (N / 2) % nranks || (N / R) % nranks) {
-        fprintf(stderr, "zeldovich_hip: cannot split PPD %lld (R=%d) over %d ranks (a power of two dividing PPD/2 and PPD/R is required)\n",
-                (long long) N, R, nranks);
-        return 1;
-    }
-    // legacy mt19937 streams, one per yres (power_spectrum.cpp:18-25); the second f_NL pass takes D from PhiK and draws nothing
-    const bool v1 = p->version == 1 && phik == nullptr;
-    if (p->version != 0 && p->version != 1 && p->version != 2) {
-        fprintf(stderr, "zeldovich_hip: ZD_Version = %d (1 or 2 expected)\n", p->version);
-        return 1;
-    }
-    if (v1 && (p->numblock <= 0 || N % p->numblock || (N / p->numblock) % nranks)) {
-        fprintf(stderr, "zeldovich_hip: ZD_Version = 1 needs ZD_NumBlock dividing PPD and PPD/NumBlock streams divisible by the number of "
-                        "ranks (%d)\n", nranks);
-        return 1;
-    }
-    zd_plan *pl = new zd_plan;
-    pl->p       = *p;
-    pl->rank    = rank;
-    pl->nranks  = nranks;
-    pl->N       = (int) N;
-    pl->half    = (int) (N / 2);
-    // (density only: one array — zeldovich.cpp:871-876 — except on the composite kernels, where it rides on the six-field ZA store)
-    pl->narray  = (phi_mode == 1 || (p->qdensity == 2 && (any_path || !dens_fields(p)))) ? 1 : (p->qPLT ? 4 : 2);
-    if (phi_mode == 0 && phik == nullptr && pl->narray >= 2 && !any_path) pl->pack = pack_mode(p, R);
-    pl->any = any_path;
-    if (zd::pack_is_fields(pl->pack) && ((pl->half / nranks) % zd::FIELD_RB || N / R > 2048))  // row blocks of 8, z FFT <= 2048
-        pl->pack = N > 4096 ? zd::PACK_NONE : (pl->pack == zd::PACK_PLTFIELD ? zd::PACK_PLT3 : zd::PACK_ZAPAIR);
-    if (N > 8192 && pl->pack != zd::PACK_ZAFIELD) {  // a 16384-point line fills a workgroup: only the field store's kernels exist (also 8640 = 64 * 135: ZA)
-        fprintf(stderr, "zeldovich_hip: PPD = %lld runs on the ZA field store only (ZD_StreamFactor >= 16; no ZD_qPLT / ZD_f_NL / ZD_qdensity = 2; "
-                        "ZD_qdensity = 1 on the composite grid 8640 only)\n",
-                (long long) N);
-        delete pl;
-        return 1;
-    }
-    if (pl->pack == zd::PACK_NONE && pow2 && (int64_t) pl->narray * (N / 16) > 1024) {
-        // (launch_xfft_t would say so only after the Z and y stages of the first pass had run)
-        fprintf(stderr, "zeldovich_hip: PPD = %lld on the reference's %d arrays (PLT with ZD_qdensity, ZD_f_NL or ZD_StoreMode = reference) has no "
-                        "x pass: the lines of a row are %lld threads\n", (long long) N, pl->narray, (long long) pl->narray * (N / 16));
-        delete pl;
-        return 1;
-    }
-    if (pl->pack != zd::PACK_NONE) pl->narray = 3;
-    pl->dens    = pl->pack == zd::PACK_ZAFIELD && dens_fields(p) && np2;
-    pl->dens_only = pl->dens && p->qdensity == 2;  // density planes only: no displacement arrays, no records (src/output.cpp:94,207)
-    if (pl->pack == zd::PACK_ZAFIELD && dens_fields(p) && !np2) {  // (cannot happen: dens_fields is composite-only)
-        delete pl;
-        return 1;
-    }
-    pl->pstep   = (pl->pack == zd::PACK_ZAPAIR || pl->pack == zd::PACK_ZAFIELD) ? 2 : 1;
-    pl->npass   = R / pl->pstep;
-    pl->R       = R;
-    pl->L       = (int) (N / R);
-    pl->Hq      = pl->half / nranks;
-    pl->Zq      = pl->L / nranks;
+}
 
+// ---- block store layout (zd_device.h StoreLayout): chunks per peer rank, ~2 MB tiles inside; work items of the fused Z stage ----
+static int plan_block_layout(zd_plan *pl, bool v1) {
+    const zd_params *p = &pl->p;
+    zd::GenConst &g = pl->g;
+    const bool main = !g.gen_phi && !g.phik;
+    zd::StoreLayout &S = pl->S;
+    S.N      = pl->N;
+    S.half   = pl->half;
+    S.Hq     = pl->Hq;
+    S.lHq    = 0;
+    while ((1 << S.lHq) < pl->Hq) S.lHq++;
+    S.lG = 0;
+    while ((1 << S.lG) < pl->nranks) S.lG++;
+    S.ky_stride = pl->nranks;
+    S.narray = pl->narray;
+    S.prune     = tune_env("ZD_PRUNE") ? atoi(tune_env("ZD_PRUNE")) : 7;  // bit 0 k_gen, 1 k_zfft, 2 k_yfft
+    S.nt = tune_env("ZD_NT") ? atoi(tune_env("ZD_NT")) : 0;
+    if (g.phik) S.prune = 0;  // f_NL second pass: every mode carries power (the zero rule is bypassed)
+    if (pl->any) S.prune = 0;  // the convolution kernels transform every column: the generator must write every one
+    S.kmax      = g.kmax;
+    S.fund2     = g.fundamental2;
+    S.k2_cutoff = p->corner_modes ? 0.0 : g.k2_cutoff;  // CornerModes: only the |k_i| == kmax rule prunes
+    {
+        S.rows_outer = 0;
+        int lBk = 20, lBz = 0;  // measured best on MI355X (profiles/r01_layout_sweep.txt): rows of one plane together
+        if (const char *env = tune_env("ZD_LAYOUT")) {  // experimentation knob: "lBk,lBz,rows_outer"
+            int a = lBk, b = lBz, o = 0;
+            if (sscanf(env, "%d,%d,%d", &a, &b, &o) >= 2) {
+                lBk = a; lBz = b; S.rows_outer = o;
+            }
+        }
+        const int max_lBk = S.lHq + 1;  // self + twin slots of a chunk in ONE block: chunks are plane-major (zd_multi.cpp
+                                        // exchanges them in plane groups)
+        while (lBk > max_lBk) lBk--;
+        while ((1 << lBz) > pl->Zq) lBz--;
+        S.lBk = lBk;
+        S.lBz = lBz;
+        S.one_block = (pl->nranks == 1 && lBk == S.lHq + 1 && lBz == 0 && !S.rows_outer) ? 1 : 0;
+        int row_pad = store_row_pad(pl->N);  // in complex elements
+        if (const char *env = tune_env("ZD_PAD")) sscanf(env, "%d", &row_pad);
+        // Fused Z stage of the packed PLT store (zd_kernels_fz.hip: generator + z FFT in one kernel, the folded inputs stay on the
+        // CU): one rank, z lines of 1024 or 512 points (PPD = 512 = BASELINE C2, 1024, or 2048 = BASELINE C3 at R = 2), the table generator's arithmetic,
+        // version-2 streams, the whole field; and the kz = N/2 plane must be dead (the kernel never draws it: true unless
+        // CornerModes is set together with ZD_k_cutoff != 1).  ZD_StoreMode = packed keeps the two-kernel stage (A/B runs).
+        // Its store interleaves 4 planes along x (StoreLayout::lq = 2) so that a lane's 4 neighbours — 4 consecutive planes of
+        // ONE column — write a 64-byte run.
+        pl->fused_z = pl->pack == zd::PACK_PLT3 && p->store_mode == ZD_STORE_AUTO && S.one_block && zd::genz_plt_supported(pl->N, pl->L)
+                      && g.genf_tab && !v1 && p->qoneslab < 0 && main && p->k_cutoff >= 1.0
+                      && (g.kmax == pl->half || !p->corner_modes) && (S.prune & 7) == 7 && !tune_env("ZD_NO_FUSED_Z");
+        S.lq         = pl->fused_z ? 2 : 0;
+        // (the pad that spreads the y stage's strided rows over the HBM channels: 24 elements per plain row; per plane row of an
+        // interleaved row 12 measured best — y stage of PPD=2048 PLT 144.5 ms at 24, 143.2 at 6, 139.7 at 12, 156.7 at 48)
+        if (S.lq && !tune_env("ZD_PAD")) row_pad = store_row_pad(pl->N) / 2;
+        S.pitch      = (pl->N + row_pad) << S.lq;
+        S.a_rows     = (1 << lBk) << lBz;
+        S.zb_rows    = S.a_rows * pl->narray;
+        S.kb_rows    = S.zb_rows * ((pl->Zq >> S.lq) >> lBz);
+        S.chunk_rows = S.kb_rows * ((2 * pl->Hq) >> lBk);
+    }
+
+    pl->ec.N        = pl->N;
+    pl->ec.narray   = pl->narray;
+    pl->ec.icformat = p->icformat;
+    pl->ec.recsize  = record_size(p->icformat);
+    pl->ec.qPLT     = p->qPLT;
+    pl->ec.qdensity = p->qdensity;
+    pl->ec.vnorm    = p->qPLT ? 1.0 : (sqrt(1. + 24 * p->f_cluster) - 1) * .25;  // output.cpp:78-82
+    pl->ec.pack     = pl->pack == zd::PACK_PLTFIELD ? zd::PACK_PLT3 : pl->pack;  // the y stage builds the PLT3 arrays in the ring
+    pl->ec.z_pair   = pl->R / 2;
+    pl->ec.xdead_lo = 1;  // (none; set below for the field stores' ring)
+    pl->ec.xdead_hi = 0;
+    pl->store_bytes_ = (int64_t) S.chunk_rows * S.pitch * pl->nranks * 16;
+    // columns no row of which survives the zero rule (column_is_zero with ky = 0): never written by the z stage, skipped by the
+    // y stage (whole tiles) and taken as zero by the x stage — power-of-two and composite kernels, every store; not the
+    // convolution path (it transforms everything) and not the f_NL passes (prune = 0)
+    if ((S.prune & 4) && !pl->any && main) {
+        int lo = 0;
+        while (lo < pl->half && !zd::column_is_zero(S, lo, 0)) lo++;
+        bool all = true;  // the rule is an interval in |kx| for every ky: check it rather than assume it
+        for (int kx = lo; kx <= pl->half && all; kx++) all = zd::column_is_zero(S, kx, 0) && zd::column_is_zero(S, -kx, 0);
+        if (all && lo >= 1) {
+            pl->ec.xdead_lo = lo;
+            pl->ec.xdead_hi = pl->N - lo;
+            S.prune |= zd::PRUNE_YTILE;  // the x kernels take zeros there: the y stage may skip those tiles
+        }
+    }
+    if (pl->fused_z) {
+        // work items of k_genz_plt: for every half-space row ky >= 1 the live columns kx in (-w, w) (zero rule: column_is_zero), cut
+        // where the draw counter of a row jumps (x = N/2 | N/2 + 1) and into pieces of at most 128 columns (a piece costs its
+        // threads one jump from the row's stream head: ~14 steps of the 2^i table against 4 x 128 draws); longest first
+        std::vector<zd::FzItem> items;
+        const int SEG = 128;
+        for (int kyl = (pl->rank == 0 ? 1 : 0); kyl < pl->Hq; kyl++) {
+            const int ky = pl->rank + pl->nranks * kyl;
+            auto add_range = [&](int xa, int xb) {  // [xa, xb): maximal runs of live columns, in pieces
+                int x = xa;
+                while (x < xb) {
+                    while (x < xb && zd::column_is_zero(S, x > pl->half ? x - pl->N : x, ky)) x++;
+                    int e = x;
+                    while (e < xb && !zd::column_is_zero(S, e > pl->half ? e - pl->N : e, ky)) e++;
+                    for (int q = x; q < e; q += SEG) items.push_back(zd::FzItem{kyl, q, std::min(SEG, e - q), 0});
+                    x = e;
+                }
+            };
+            add_range(0, pl->half + 1);
+            add_range(pl->half + 1, pl->N);
+        }
+        std::stable_sort(items.begin(), items.end(), [](const zd::FzItem &a, const zd::FzItem &b) { return a.n > b.n; });
+        pl->n_fzitems = (unsigned) items.size();
+        if (!items.empty()) {
+            HIPCHECK(hipMalloc((void **) &pl->d_fzitems, sizeof(zd::FzItem) * items.size()));
+            HIPCHECK(hipMemcpy(pl->d_fzitems, items.data(), sizeof(zd::FzItem) * items.size(), hipMemcpyHostToDevice));
+        }
+        int dev = 0;
+        hipGetDevice(&dev);
+        hipDeviceGetAttribute(&pl->ncu, hipDeviceAttributeMultiprocessorCount, dev);
+        if (pl->ncu < 1) pl->ncu = 256;
+    }
+    return 0;
+}
+
+// ---- the store: the reference arrays as a simple [plane][array][y][x] store with tables for the z lines (length L) and the y / x
+// lines (length N) — composite twiddles where the route says so (f_NL on the composite grids), Bluestein tables otherwise; a field
+// store and the ring between its y and x stages ----
+static int plan_stores(zd_plan *pl, bool twr) {
+    if (pl->any) {
+        if (twr) {
+            if (upload_twq(pl->N, &pl->d_twr_n) || upload_twq(pl->L, &pl->d_twr_l)) {
+                fprintf(stderr, "zeldovich_hip: composite twiddle tables failed\n");
+                return 1;
+            }
+        } else if (any_make_tab(pl->L, &pl->tabL, pl->d_any) || any_make_tab(pl->N, &pl->tabN, pl->d_any + 3)) {
+            return 1;
+        }
+        pl->AL.N         = pl->N;
+        pl->AL.pitch     = pl->N + store_row_pad(pl->N);
+        pl->AL.narray    = pl->narray;
+        pl->store_bytes_ = (int64_t) pl->L * pl->narray * pl->N * pl->AL.pitch * 16;
+        if (pl->nranks > 1) {  // [chunk = peer rank][local plane][array][row slot < 2 Hq][x]: 1 / G of the one-rank store
+            pl->AC           = zd::AnyChunks{pl->N, pl->AL.pitch, pl->narray, pl->nranks, pl->Hq, pl->Zq, 0};
+            pl->AC.chunk     = (long long) pl->Zq * pl->narray * 2 * pl->Hq * pl->AL.pitch;
+            pl->store_bytes_ = (int64_t) pl->nranks * pl->AC.chunk * 16;
+        }
+    }
+    if (!zd::pack_is_fields(pl->pack)) return 0;
+    zd::StoreLayout &S = pl->S;
+    std::vector<zd::FieldRow> rows;
+    const int64_t fe = field_rows(&pl->p, pl->nranks, &rows);
+    HIPCHECK(hipMalloc((void **) &pl->d_fieldrows, sizeof(zd::FieldRow) * rows.size()));
+    HIPCHECK(hipMemcpy(pl->d_fieldrows, rows.data(), sizeof(zd::FieldRow) * rows.size(), hipMemcpyHostToDevice));
+    pl->F.lG          = S.lG;
+    pl->F.lZq         = 0;
+    while ((1 << pl->F.lZq) < pl->Zq) pl->F.lZq++;
+    pl->F.Zq          = pl->Zq;
+    pl->F.field_elems = fe;
+    pl->F.ndens       = pl->dens ? 2 : 0;
+    pl->F.nfield      = pl->pack == zd::PACK_PLTFIELD ? 6 : 4 + pl->F.ndens;
+    pl->F.chunk_elems = (int64_t) pl->Zq * pl->F.nfield * fe;
+    pl->F.rows        = pl->d_fieldrows;
+    pl->store_bytes_  = pl->F.chunk_elems * pl->nranks * 16;
+    // ring: `ring_planes` store planes of the three arrays, laid out as a single-rank block store (one_block)
+    pl->ring_planes = field_ring_planes(pl->N, pl->Zq);
+    zd::StoreLayout &Q = pl->SR;
+    Q            = S;
+    Q.lq         = 0;
+    Q.Hq         = pl->half;
+    Q.lHq        = 0;
+    while ((1 << Q.lHq) < pl->half) Q.lHq++;
+    Q.lG         = 0;
+    Q.ky_stride  = 1;
+    Q.narray     = 3;
+    Q.lBk        = Q.lHq + 1;
+    Q.lBz        = 0;
+    Q.rows_outer = 0;
+    Q.one_block  = 1;
+    Q.prune      = 0;
+    Q.pitch      = pl->N + store_row_pad(pl->N);
+    Q.a_rows     = pl->N;
+    Q.zb_rows    = 3 * pl->N;
+    Q.kb_rows    = Q.zb_rows * pl->ring_planes;
+    Q.chunk_rows = Q.kb_rows;
+    HIPCHECK(zd_store_alloc((void **) &pl->d_ring, (size_t) Q.chunk_rows * Q.pitch * 16));
+    if (pl->dens)  // the density array delta_r0 + i delta_r1 of the ring's planes: [plane][y][x]
+        HIPCHECK(zd_store_alloc((void **) &pl->d_ring_dens, (size_t) pl->ring_planes * pl->N * Q.pitch * 16));
+    return 0;
+}
+
+// ---- folded-input slabs (two, for the gen||zfft overlap): enough rows per launch to fill the chip ----
+static int plan_slabs(zd_plan *pl, bool v1, int64_t eig_ppd) {
+    const zd_params *p = &pl->p;
+    zd::GenConst &g = pl->g;
+    const int64_t N = pl->N;
+    const int64_t row_b = y_bytes_per_row(pl);
+    int64_t slab_b = (int64_t) 3 << 29;  // ~1.5 GB per buffer
+    if (const char *env = tune_env("ZD_SLAB_MB")) slab_b = (int64_t) atoll(env) << 20;
+#ifdef ZD_SLAB_MB_FORCE  // experiment (make variant)
+    slab_b = (int64_t) ZD_SLAB_MB_FORCE << 20;
+#endif
+    int rows = (int) std::max<int64_t>(1, slab_b / row_b);
+    rows     = std::min(rows, pl->Hq);
+    if (zd::pack_is_fields(pl->pack)) {  // whole row blocks
+        rows = std::max(zd::FIELD_RB, rows / zd::FIELD_RB * zd::FIELD_RB);
+        while (pl->Hq % rows) rows -= zd::FIELD_RB;
+    }
+    if (v1) {  // the accepted pairs of a slab: N^2 x 16 B per row, <= ~4 GB
+        const int minr = zd::pack_is_fields(pl->pack) ? zd::FIELD_RB : 1;
+        rows = std::max<int64_t>(minr, std::min<int64_t>(rows, ((int64_t) 4 << 30) / (N * N * 16)));
+        if (zd::pack_is_fields(pl->pack)) rows = rows / zd::FIELD_RB * zd::FIELD_RB;
+    }
+    while (pl->Hq % rows) rows--;
+    pl->slab_rows = rows;
+    pl->overlap   = p->serial_z == 0 && !v1 && !pl->any;  // version 1: the streams are sequential in ky
+    // PLT with a table that is interpolated (eig_ppd does not divide into PPD): the (x, y) part of the trilinear lookup is
+    // done once per column of a slab (k_eig_lines) instead of once per mode; one slab of lines, refilled on the generator's
+    // stream in front of every generator launch
+    if (g.qPLT && g.genf_tab && !v1 && eig_ppd % N != 0) {
+        const size_t nb = (size_t) (eig_ppd / 2 + 1) * rows * N * 4 * sizeof(double);
+        if (nb <= ((size_t) 1 << 30)) {
+            HIPCHECK(hipMalloc((void **) &pl->d_eiglines, nb));
+            g.eig_lines = pl->d_eiglines;
+            g.eig_rows  = rows;
+        }
+    }
+    if (v1) {
+        pl->v1_block = (int) (N / p->numblock);
+        HIPCHECK(hipMalloc((void **) &pl->d_v1streams, sizeof(zd::V1Stream) * (size_t) pl->v1_block));
+        HIPCHECK(hipMalloc((void **) &pl->d_v1dev, (size_t) rows * N * N * sizeof(double2)));
+        HIPCHECK(hipMalloc((void **) &pl->d_v1err, sizeof(int)));
+        HIPCHECK(hipMemset(pl->d_v1err, 0, sizeof(int)));
+        g.v1dev = pl->d_v1dev;
+    }
+    // k_genf is a persistent kernel: a few workgroups per CU pull tiles from a counter (one per launch).  With
+    // the second stream active the grid is kept small enough that a k_zfft workgroup (64 KB LDS, 2 waves/SIMD)
+    // always fits beside the generator's waves on every CU.
+    {
+        int dev = 0, ncu = 256;
+        hipGetDevice(&dev);
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+        int per_cu = pl->overlap ? 3 : 6;
+        if (const char *env = tune_env("ZD_GEN_WGS")) per_cu = atoi(env);
+#ifdef ZD_GEN_WGS_FORCE  // experiment (make variant)
+        if (pl->overlap) per_cu = ZD_GEN_WGS_FORCE;
+#endif
+        pl->gen_max_wgs = std::max(1, per_cu) * std::max(1, ncu);
+        pl->n_tilectr   = 2 * (pl->Hq / rows) + 2;  // per pass parity: the next pass's generator may already run
+        HIPCHECK(hipMalloc((void **) &pl->d_tilectr, sizeof(unsigned) * pl->n_tilectr));
+    }
+    // ring size: 1 slab without the overlap, else 2 + what the store (allocated by the caller afterwards) leaves
+    int K = 1;
+    if (pl->overlap) {
+        K = 2;
+        const int nslab = pl->Hq / rows;
+        // Measured (PPD=4096 ZA, 60 slabs ahead): no gain — the generator's resident workgroups take LDS and
+        // registers from k_yfft (128 KB LDS per workgroup at PPD=4096), which slows down by what the z stage gains.
+        // The larger ring therefore stays an experiment: ZD_Y_AHEAD=1 sizes it from free HBM, ZD_Y_SLABS=n fixes it.
+        if (tune_env("ZD_Y_AHEAD") && pl->npass > 1 && nslab > 2) {
+            size_t free_b = 0, total_b = 0;
+            hipMemGetInfo(&free_b, &total_b);
+            const int64_t reserve = zd_plan_exchange_bytes(pl) * (pl->nranks > 1 ? 2 : 1) + ((int64_t) 8 << 30);
+            const int64_t spare   = (int64_t) free_b - reserve;
+            if (spare > 0) K = (int) std::max<int64_t>(2, std::min<int64_t>(nslab, spare / (row_b * rows)));
+        }
+        if (const char *env = tune_env("ZD_Y_SLABS")) K = std::max(2, atoi(env));
+    }
+    pl->d_Y.assign(K, nullptr);
+    for (int i = 0; i < K; i++) HIPCHECK(hipMalloc((void **) &pl->d_Y[i], (size_t) row_b * rows));
+    if (pl->overlap) {
+#ifdef ZD_TUNING
+        // A/B (VERDICT r4 #5 i): ZD_CU_SPLIT = n gives the z FFT's stream n CUs of every XCD's 32 and the generator's stream
+        // the other 32 - n (hipExtStreamCreateWithCUMask; CU c of the mask = XCD c % 8, CU c / 8 of it on this part)
+        if (const char *env = tune_env("ZD_CU_SPLIT")) {
+            const int nf = std::max(1, std::min(31, atoi(env)));
+            uint32_t mg[8] = {0}, mf[8] = {0};
+            for (int c = 0; c < 256; c++) ((c / 8) < nf ? mf : mg)[c / 32] |= 1u << (c % 32);
+            HIPCHECK(hipExtStreamCreateWithCUMask(&pl->s_gen, 8, mg));
+            HIPCHECK(hipExtStreamCreateWithCUMask(&pl->s_fft, 8, mf));
+        } else
+#endif
+        {
+            HIPCHECK(hipStreamCreateWithFlags(&pl->s_gen, hipStreamNonBlocking));
+            HIPCHECK(hipStreamCreateWithFlags(&pl->s_fft, hipStreamNonBlocking));
+        }
+        HIPCHECK(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
+        pl->ev_gen.assign(K, nullptr);
+        pl->ev_fft.assign(K, nullptr);
+        for (int i = 0; i < K; i++) {
+            HIPCHECK(hipEventCreateWithFlags(&pl->ev_gen[i], hipEventDisableTiming));
+            HIPCHECK(hipEventCreateWithFlags(&pl->ev_fft[i], hipEventDisableTiming));
+        }
+    }
+    return 0;
+}
+
+// a plan of the shape an accepted route gives; each part above fills its own members; a plan that fails half-way is destroyed here, once
+static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
+                           int role, const cplx *phik, zd_plan **out) {
+    zd_plan *pl   = new zd_plan;
+    pl->p         = *p;
+    pl->rank      = rank;
+    pl->nranks    = nranks;
+    pl->N         = (int) p->ppd;
+    pl->half      = pl->N / 2;
+    pl->any       = rt.family >= zd::FAM_REF_COMPOSITE;
+    pl->pack      = rt.pack;
+    pl->narray    = rt.narray;
+    pl->dens      = rt.dens;
+    pl->dens_only = rt.dens_only;
+    pl->pstep     = rt.pstep;
+    pl->npass     = rt.npass;
+    pl->R         = rt.R;
+    pl->L         = rt.L;
+    pl->Hq        = rt.Hq;
+    pl->Zq        = rt.Zq;
+    const bool v1 = p->version == 1 && phik == nullptr;  // (the second f_NL pass takes D from PhiK and draws nothing)
     // ---- generator constants (zeldovich.cpp:299-320, 350) ----
     zd::GenConst &g = pl->g;
     memset(&g, 0, sizeof(g));
@@ -1054,495 +1278,47 @@ static int plan_create_one(const zd_params *p, const zd_pk *pk, const double *ei
         g.ln_growth_ratio = log(a_NL / a0);
     }
     g.eig_ppd = eig_ppd;
-    g.gen_phi = phi_mode == 1;
+    g.gen_phi = role == zd::ROLE_PHI;
     g.phik    = phik;
-    if (phi_mode == 1) g.qPLT = 0;  // the phi pass stops before the displacement algebra (zeldovich.cpp:385-391)
-
-#define PLCHECK(call)                                                                             \
-    do {                                                                                          \
-        hipError_t e__ = (call);                                                                  \
-        if (e__ != hipSuccess) {                                                                  \
-            fprintf(stderr, "zeldovich_hip: %s failed at %s:%d: %s\n", #call, __FILE__, __LINE__, \
-                    hipGetErrorString(e__));                                                      \
-            zd_plan_destroy(pl);                                                                  \
-            return 1;                                                                             \
-        }                                                                                         \
-    } while (0)
-
-    if (!pk->is_powerlaw) {
-        PLCHECK(hipMalloc((void **) &pl->d_pk, sizeof(double) * 3 * (size_t) pk->n));
-        PLCHECK(hipMemcpy(pl->d_pk, pk->x, sizeof(double) * pk->n, hipMemcpyHostToDevice));
-        PLCHECK(hipMemcpy(pl->d_pk + pk->n, pk->y, sizeof(double) * pk->n, hipMemcpyHostToDevice));
-        PLCHECK(hipMemcpy(pl->d_pk + 2 * pk->n, pk->y2, sizeof(double) * pk->n, hipMemcpyHostToDevice));
-        g.pk_x  = pl->d_pk;
-        g.pk_y  = pl->d_pk + pk->n;
-        g.pk_y2 = pl->d_pk + 2 * pk->n;
-        // segment start table: cell c covers ln k in [x0 + c*dx, x0 + (c+1)*dx)
-        std::vector<int> lut(zd::PK_LUT);
-        const double x0 = pk->x[0], x1 = pk->x[pk->n - 1];
-        const double dx = (x1 - x0) / zd::PK_LUT;
-        int klo = 0;
-        for (int c2 = 0; c2 < zd::PK_LUT; c2++) {
-            const double cell_start = x0 + c2 * dx * (1.0 - 1e-12) - 1e-9;  // never past the true start
-            while (klo < pk->n - 2 && pk->x[klo + 1] <= cell_start) klo++;
-            lut[c2] = klo;
-        }
-        PLCHECK(hipMalloc((void **) &pl->d_lut, sizeof(int) * lut.size()));
-        PLCHECK(hipMemcpy(pl->d_lut, lut.data(), sizeof(int) * lut.size(), hipMemcpyHostToDevice));
-        g.pk_lut     = pl->d_lut;
-        g.lut_x0     = x0;
-        g.lut_inv_dx = 1.0 / dx;
+    if (role == zd::ROLE_PHI) g.qPLT = 0;  // the phi pass stops before the displacement algebra (zeldovich.cpp:385-391)
+    plan_zstage_jobs(pl);
+    if (plan_device_tables(pl, pk, eig, eig_ppd) || plan_block_layout(pl, v1) || plan_stores(pl, rt.twr) || plan_slabs(pl, v1, eig_ppd)) {
+        zd_plan_destroy(pl);
+        return 1;
     }
-    if (p->qPLT) {
-        const size_t nb = sizeof(double) * (size_t) eig_ppd * eig_ppd * (eig_ppd / 2 + 1) * 4;
-        PLCHECK(hipMalloc((void **) &pl->d_eig, nb));
-        PLCHECK(hipMemcpy(pl->d_eig, eig, nb, hipMemcpyHostToDevice));
-        g.eig = pl->d_eig;
-    }
-    // per-plane stream heads == v2rng[] of the reference (power_spectrum.cpp:26-37)
-    {
-        std::vector<u128> rows(pl->half);
-        const zdpcg::Affine plane = zdpcg::jump_map((u128) 2 * ZD_MAX_PPD * ZD_MAX_PPD);
-        rows[0] = zdpcg::seed_state((uint64_t) p->seed);
-        for (int i = 1; i < pl->half; i++) rows[i] = zdpcg::apply(plane, rows[i - 1]);
-        PLCHECK(hipMalloc((void **) &pl->d_rowstate, sizeof(u128) * rows.size()));
-        PLCHECK(hipMemcpy(pl->d_rowstate, rows.data(), sizeof(u128) * rows.size(), hipMemcpyHostToDevice));
-        g.row_state = pl->d_rowstate;
-        // (built once; ZD_NumGPU creates its plans from several host threads at a time)
-        static const zdpcg::BitTable bt = [] {
-            zdpcg::BitTable b;
-            zdpcg::make_bit_table(b);
-            return b;
-        }();
-        if (zdk_upload_bit_table(&bt) != 0 || zdk_upload_bit_table_fz(&bt) != 0) {
-            fprintf(stderr, "zeldovich_hip: uploading the RNG jump table failed\n");
-            zd_plan_destroy(pl);
-            return 1;
-        }
-        // z-walk of k_gen (see zd_device.h GenJumps): forward L rows inside a fold, then back to the
-        // first term of the next k2; crossing z = N/2 shifts the counter row by +-(65536 - N)
-        const long long wrap = 65536 - N, Lr = pl->L, back = -((long long) (R - 1) * Lr - 1);
-        pl->J.fwd[0]  = row_jump(Lr);
-        pl->J.fwd[1]  = row_jump(Lr + wrap);
-        pl->J.back[0] = row_jump(back);
-        pl->J.back[1] = row_jump(back > 0 ? back + wrap : back - wrap);
-        pl->J.fwd_full[0]  = row_jump_full(Lr);
-        pl->J.fwd_full[1]  = row_jump_full(Lr + wrap);
-        pl->J.back_full[0] = row_jump_full(back);
-        pl->J.back_full[1] = row_jump_full(back > 0 ? back + wrap : back - wrap);
-        // the mirrored walker of genf_tile_kz: the same moves negated (crossing z = N/2 in its own direction of motion)
-        const long long mf = -Lr, mb = -back;
-        pl->J.mfwd[0]       = row_jump(mf);
-        pl->J.mfwd[1]       = row_jump(mf - wrap);
-        pl->J.mback[0]      = row_jump(mb);
-        pl->J.mback[1]      = row_jump(mb > 0 ? mb + wrap : mb - wrap);
-        pl->J.mfwd_full[0]  = row_jump_full(mf);
-        pl->J.mfwd_full[1]  = row_jump_full(mf - wrap);
-        pl->J.mback_full[0] = row_jump_full(mb);
-        pl->J.mback_full[1] = row_jump_full(mb > 0 ? mb + wrap : mb - wrap);
-    }
-    {
-        std::vector<cplx> twN = make_twiddles(pl->N), twL = make_twiddles(pl->L);
-        PLCHECK(hipMalloc((void **) &pl->d_twN, sizeof(cplx) * twN.size()));
-        PLCHECK(hipMemcpy(pl->d_twN, twN.data(), sizeof(cplx) * twN.size(), hipMemcpyHostToDevice));
-        PLCHECK(hipMalloc((void **) &pl->d_twL, sizeof(cplx) * twL.size()));
-        PLCHECK(hipMemcpy(pl->d_twL, twL.data(), sizeof(cplx) * twL.size(), hipMemcpyHostToDevice));
-        if (np2) {  // composite transforms (zd_fft_q.h): exp(2 pi i k / P) | exp(2 pi i k / len) | exp(2 pi i k / Q) per length
-            if (upload_twq(pl->N, &pl->d_twq_n) || upload_twq(pl->L, &pl->d_twq_l)) {
-                fprintf(stderr, "zeldovich_hip: composite twiddle tables failed\n");
-                zd_plan_destroy(pl);
-                return 1;
-            }
-        }
-        // LDS image of k_genf (layout: GenfTab in zd_kernels.hip).  Spline tables beyond 512 segments do not
-        // fit: such runs use the general generator.
-        const int nseg = pk->is_powerlaw ? 0 : pk->n - 1;
-        if (nseg <= 512 && !tune_env("ZD_GEN_GENERAL")) {
-            std::vector<double> T = build_genf_table(pk, nseg, &g.glut_x0, &g.glut_inv_dx);
-            PLCHECK(hipMalloc((void **) &pl->d_genf, sizeof(double) * T.size()));
-            PLCHECK(hipMemcpy(pl->d_genf, T.data(), sizeof(double) * T.size(), hipMemcpyHostToDevice));
-            g.genf_tab  = pl->d_genf;
-            g.genf_n    = (int) T.size();
-            g.genf_nseg = nseg;
-        }
-    }
-    // {P, 1/k^2} table over the integer |k|^2 that can carry power (zero rule of zeldovich.cpp:350-353)
-    if (!tune_env("ZD_NO_PKTAB")) {
-        const double half2 = (double) pl->half * pl->half;
-        double nmax = p->corner_modes ? 3.0 * half2 : std::min(3.0 * half2, g.k2_cutoff / g.fundamental2 * (1 + 1e-9) + 2);
-        const long long n = (long long) nmax + 2;
-        if (n <= ((long long) 1 << 26)) {
-            PLCHECK(hipMalloc((void **) &pl->d_pktab, sizeof(double) * 2 * (size_t) n));
-            if (zd::launch_pk_table(g, (int) n, pl->d_pktab, 0)) {
-                zd_plan_destroy(pl);
-                return 1;
-            }
-            PLCHECK(hipDeviceSynchronize());
-            g.pk_tab = (const double2 *) pl->d_pktab;
-        }
-    }
-    if (phi_mode == 1 || phik) {  // M(k) = 2 g c^2 T(k) k^2 / (3 Omega_M H0^2), zeldovich.cpp:377-383
-        const double H0 = 100., c = 299792.458, growth = 1. / (1 + p->z_initial);
-        g.fnl_pre = 2. * growth * c * c;
-        g.fnl_den = 3. * p->Omega_M * H0 * H0;
-        g.n_s     = p->n_s;
-        // Normalize(): primordial_norm = power(kmin) / primordial_power(kmin) with norm 1 (power_spectrum.cpp:221-222)
-        g.primordial_norm = zd_pk_power(pk, pk->kmin) / (1. * exp(log(pk->kmin) * p->n_s));
-        const long long n = 3LL * pl->half * pl->half + 2;
-        PLCHECK(hipMalloc((void **) &pl->d_fnlM, sizeof(double) * (size_t) n));
-        if (zd::launch_fnl_table(g, (int) n, pl->d_fnlM, 0)) {
-            zd_plan_destroy(pl);
-            return 1;
-        }
-        PLCHECK(hipDeviceSynchronize());
-        g.fnl_M = pl->d_fnlM;
-    }
-    PLCHECK(hipMalloc((void **) &pl->d_red, sizeof(zd::Reduce)));
-    PLCHECK(hipMemset(pl->d_red, 0, sizeof(zd::Reduce)));
-
-    // ---- jobs of the z stage ----
-    {
-        zd::JobList &jl = pl->jobs;
-        memset(&jl, 0, sizeof(jl));
-        jl.pack = pl->pack;
-        auto add = [&](int kind, int arr, int twin, int res) {
-            jl.kind[jl.n] = kind;
-            jl.arr[jl.n]  = arr;
-            jl.twin[jl.n] = twin;
-            jl.res[jl.n]  = res;
-            jl.n++;
-        };
-        if (pl->pack == zd::PACK_PLTFIELD) {  // the six sums (k_zfft_f: job index = field index)
-            add(zd::JOB_PX, 0, 0, 0);
-            add(zd::JOB_PY, 1, 0, 0);
-            add(zd::JOB_PZ, 2, 0, 0);
-            add(zd::JOB_PFX, 3, 0, 0);
-            add(zd::JOB_PFY, 4, 0, 0);
-            add(zd::JOB_PFZ, 5, 0, 0);
-        } else if (pl->pack == zd::PACK_ZAFIELD) {  // the potentials E, Z of the two residues (k_zfft_f: job index = field index)
-            add(zd::JOB_E, 0, 0, 0);
-            add(zd::JOB_Z, 1, 0, 0);
-            add(zd::JOB_E, 2, 0, 1);
-            add(zd::JOB_Z, 3, 0, 1);
-            if (pl->dens) {  // ZD_qdensity = 1: the density sums of the two residues
-                add(zd::JOB_DENS, 4, 0, 0);
-                add(zd::JOB_DENS, 5, 0, 1);
-            }
-        } else if (pl->pack == zd::PACK_ZAPAIR) {  // (qy + i qz)_r0 | (qy + i qz)_r1 | qx_r0 + i qx_r1
-            add(zd::JOB_B_SELF, 0, 0, 0);
-            add(zd::JOB_B_TWIN, 0, 1, 0);
-            add(zd::JOB_B_SELF, 1, 0, 1);
-            add(zd::JOB_B_TWIN, 1, 1, 1);
-            add(zd::JOB_FX, 2, 0, 0);  // generator output slot 4 = X_self, slot 5 = X_twin input (k_gen/k_genf combine F_x(r0), F_x(r1))
-            add(zd::JOB_FX, 2, 1, 1);
-        } else if (pl->pack == zd::PACK_PLT3) {  // qx + i vx | qy + i qz | vy + i vz
-            add(zd::JOB_XV_SELF, 0, 0, 0);
-            add(zd::JOB_XV_TWIN, 0, 1, 0);
-            add(zd::JOB_B_SELF, 1, 0, 0);
-            add(zd::JOB_B_TWIN, 1, 1, 0);
-            add(zd::JOB_D_SELF, 2, 0, 0);
-            add(zd::JOB_D_TWIN, 2, 1, 0);
-        } else if (pl->narray == 1) {
-            add(zd::JOB_DENS, 0, 0, 0);
-        } else {
-            add(zd::JOB_A_SELF, 0, 0, 0);
-            add(zd::JOB_A_TWIN, 0, 1, 0);
-            add(zd::JOB_B_SELF, 1, 0, 0);
-            add(zd::JOB_B_TWIN, 1, 1, 0);
-            if (pl->narray == 4) {
-                add(zd::JOB_C_BOTH, 2, 0, 0);
-                add(zd::JOB_D_SELF, 3, 0, 0);
-                add(zd::JOB_D_TWIN, 3, 1, 0);
-            }
-        }
-    }
-    // ---- block store layout (zd_device.h StoreLayout): chunks per peer rank, ~2 MB tiles inside ----
-    zd::StoreLayout &S = pl->S;
-    S.N      = pl->N;
-    S.half   = pl->half;
-    S.Hq     = pl->Hq;
-    S.lHq    = 0;
-    while ((1 << S.lHq) < pl->Hq) S.lHq++;
-    S.lG = 0;
-    while ((1 << S.lG) < nranks) S.lG++;
-    S.ky_stride = nranks;
-    S.narray = pl->narray;
-    S.prune     = tune_env("ZD_PRUNE") ? atoi(tune_env("ZD_PRUNE")) : 7;  // bit 0 k_gen, 1 k_zfft, 2 k_yfft
-    S.nt = tune_env("ZD_NT") ? atoi(tune_env("ZD_NT")) : 0;
-    if (phik) S.prune = 0;  // f_NL second pass: every mode carries power (the zero rule is bypassed)
-    if (any_path) S.prune = 0;  // the convolution kernels transform every column: the generator must write every one
-    S.kmax      = g.kmax;
-    S.fund2     = g.fundamental2;
-    S.k2_cutoff = p->corner_modes ? 0.0 : g.k2_cutoff;  // CornerModes: only the |k_i| == kmax rule prunes
-    {
-        const long long target = std::max<long long>(1, ((long long) 2 << 20) / ((long long) pl->N * 16));
-        int lt = 0;
-        while ((1LL << (lt + 1)) <= target) lt++;
-        int lBk = (lt + 1) / 2, lBz = lt - lBk;
-        S.rows_outer = 0;
-        lBk = 20; lBz = 0;  // measured best on MI355X (profiles/r01_layout_sweep.txt): rows of one plane together
-        if (const char *env = tune_env("ZD_LAYOUT")) {  // experimentation knob: "lBk,lBz,rows_outer"
-            int a = lBk, b = lBz, o = 0;
-            if (sscanf(env, "%d,%d,%d", &a, &b, &o) >= 2) {
-                lBk = a; lBz = b; S.rows_outer = o;
-            }
-        }
-        const int max_lBk = S.lHq + 1;  // self + twin slots of a chunk in ONE block: chunks are plane-major (zd_multi.cpp
-                                        // exchanges them in plane groups)
-        while (lBk > max_lBk) lBk--;
-        while ((1 << lBz) > pl->Zq) lBz--;
-        S.lBk = lBk;
-        S.lBz = lBz;
-        S.one_block = (nranks == 1 && lBk == S.lHq + 1 && lBz == 0 && !S.rows_outer) ? 1 : 0;
-        int row_pad = store_row_pad(pl->N);  // in complex elements
-        if (const char *env = tune_env("ZD_PAD")) sscanf(env, "%d", &row_pad);
-        // Fused Z stage of the packed PLT store (zd_kernels_fz.hip: generator + z FFT in one kernel, the folded inputs stay on the
-        // CU): one rank, z lines of 1024 or 512 points (PPD = 512 = BASELINE C2, 1024, or 2048 = BASELINE C3 at R = 2), the table generator's arithmetic,
-        // version-2 streams, the whole field; and the kz = N/2 plane must be dead (the kernel never draws it: true unless
-        // CornerModes is set together with ZD_k_cutoff != 1).  ZD_StoreMode = packed keeps the two-kernel stage (A/B runs).
-        // Its store interleaves 4 planes along x (StoreLayout::lq = 2) so that a lane's 4 neighbours — 4 consecutive planes of
-        // ONE column — write a 64-byte run.
-        pl->fused_z = pl->pack == zd::PACK_PLT3 && p->store_mode == ZD_STORE_AUTO && S.one_block && zd::genz_plt_supported(pl->N, pl->L)
-                      && g.genf_tab && !v1 && p->qoneslab < 0 && phi_mode == 0 && phik == nullptr && p->k_cutoff >= 1.0
-                      && (g.kmax == pl->half || !p->corner_modes) && (S.prune & 7) == 7 && !tune_env("ZD_NO_FUSED_Z");
-        S.lq         = pl->fused_z ? 2 : 0;
-        // (the pad that spreads the y stage's strided rows over the HBM channels: 24 elements per plain row; per plane row of an
-        // interleaved row 12 measured best — y stage of PPD=2048 PLT 144.5 ms at 24, 143.2 at 6, 139.7 at 12, 156.7 at 48)
-        if (S.lq && !tune_env("ZD_PAD")) row_pad = store_row_pad(pl->N) / 2;
-        S.pitch      = (pl->N + row_pad) << S.lq;
-        S.a_rows     = (1 << lBk) << lBz;
-        S.zb_rows    = S.a_rows * pl->narray;
-        S.kb_rows    = S.zb_rows * ((pl->Zq >> S.lq) >> lBz);
-        S.chunk_rows = S.kb_rows * ((2 * pl->Hq) >> lBk);
-    }
-
-    pl->ec.N        = pl->N;
-    pl->ec.narray   = pl->narray;
-    pl->ec.icformat = p->icformat;
-    pl->ec.recsize  = record_size(p->icformat);
-    pl->ec.qPLT     = p->qPLT;
-    pl->ec.qdensity = p->qdensity;
-    pl->ec.vnorm    = p->qPLT ? 1.0 : (sqrt(1. + 24 * p->f_cluster) - 1) * .25;  // output.cpp:78-82
-    pl->ec.pack     = pl->pack == zd::PACK_PLTFIELD ? zd::PACK_PLT3 : pl->pack;  // the y stage builds the PLT3 arrays in the ring
-    pl->ec.z_pair   = R / 2;
-    pl->ec.xdead_lo = 1;  // (none; set below for the field stores' ring)
-    pl->ec.xdead_hi = 0;
-    pl->store_bytes_ = (int64_t) S.chunk_rows * S.pitch * nranks * 16;
-    if (zd::pack_is_fields(pl->pack)) {
-        std::vector<zd::FieldRow> rows;
-        const int64_t fe = field_rows(p, nranks, &rows);
-        PLCHECK(hipMalloc((void **) &pl->d_fieldrows, sizeof(zd::FieldRow) * rows.size()));
-        PLCHECK(hipMemcpy(pl->d_fieldrows, rows.data(), sizeof(zd::FieldRow) * rows.size(), hipMemcpyHostToDevice));
-        pl->F.lG          = S.lG;
-        pl->F.lZq         = 0;
-        while ((1 << pl->F.lZq) < pl->Zq) pl->F.lZq++;
-        pl->F.Zq          = pl->Zq;
-        pl->F.field_elems = fe;
-        pl->F.ndens       = pl->dens ? 2 : 0;
-        pl->F.nfield      = pl->pack == zd::PACK_PLTFIELD ? 6 : 4 + pl->F.ndens;
-        pl->F.chunk_elems = (int64_t) pl->Zq * pl->F.nfield * fe;
-        pl->F.rows        = pl->d_fieldrows;
-        pl->store_bytes_  = pl->F.chunk_elems * nranks * 16;
-        // ring: `ring_planes` store planes of the three arrays, laid out as a single-rank block store (one_block)
-        pl->ring_planes = field_ring_planes(pl->N, pl->Zq);
-        zd::StoreLayout &Q = pl->SR;
-        Q            = S;
-        Q.lq         = 0;
-        Q.Hq         = pl->half;
-        Q.lHq        = 0;
-        while ((1 << Q.lHq) < pl->half) Q.lHq++;
-        Q.lG         = 0;
-        Q.ky_stride  = 1;
-        Q.narray     = 3;
-        Q.lBk        = Q.lHq + 1;
-        Q.lBz        = 0;
-        Q.rows_outer = 0;
-        Q.one_block  = 1;
-        Q.prune      = 0;
-        Q.pitch      = pl->N + store_row_pad(pl->N);
-        Q.a_rows     = pl->N;
-        Q.zb_rows    = 3 * pl->N;
-        Q.kb_rows    = Q.zb_rows * pl->ring_planes;
-        Q.chunk_rows = Q.kb_rows;
-        PLCHECK(zd_store_alloc((void **) &pl->d_ring, (size_t) Q.chunk_rows * Q.pitch * 16));
-        if (pl->dens)  // the density array delta_r0 + i delta_r1 of the ring's planes: [plane][y][x]
-            PLCHECK(zd_store_alloc((void **) &pl->d_ring_dens, (size_t) pl->ring_planes * pl->N * Q.pitch * 16));
-
-    }
-    // columns no row of which survives the zero rule (column_is_zero with ky = 0): never written by the z stage, skipped by the
-    // y stage (whole tiles) and taken as zero by the x stage — power-of-two and composite kernels, every store; not the
-    // convolution path (it transforms everything) and not the f_NL passes (prune = 0)
-    if ((S.prune & 4) && !any_path && phi_mode == 0 && phik == nullptr) {
-        int lo = 0;
-        while (lo < pl->half && !zd::column_is_zero(S, lo, 0)) lo++;
-        bool all = true;  // the rule is an interval in |kx| for every ky: check it rather than assume it
-        for (int kx = lo; kx <= pl->half && all; kx++) all = zd::column_is_zero(S, kx, 0) && zd::column_is_zero(S, -kx, 0);
-        if (all && lo >= 1) {
-            pl->ec.xdead_lo = lo;
-            pl->ec.xdead_hi = pl->N - lo;
-            S.prune |= zd::PRUNE_YTILE;  // the x kernels take zeros there: the y stage may skip those tiles
-        }
-    }
-    g.var_slots     = pl->d_red->sumsq;
-    if (pl->fused_z) {
-        // work items of k_genz_plt: for every half-space row ky >= 1 the live columns kx in (-w, w) (zero rule: column_is_zero), cut
-        // where the draw counter of a row jumps (x = N/2 | N/2 + 1) and into pieces of at most 128 columns (a piece costs its
-        // threads one jump from the row's stream head: ~14 steps of the 2^i table against 4 x 128 draws); longest first
-        std::vector<zd::FzItem> items;
-        const int SEG = 128;
-        for (int kyl = (rank == 0 ? 1 : 0); kyl < pl->Hq; kyl++) {
-            const int ky = rank + nranks * kyl;
-            auto add_range = [&](int xa, int xb) {  // [xa, xb): maximal runs of live columns, in pieces
-                int x = xa;
-                while (x < xb) {
-                    while (x < xb && zd::column_is_zero(S, x > pl->half ? x - pl->N : x, ky)) x++;
-                    int e = x;
-                    while (e < xb && !zd::column_is_zero(S, e > pl->half ? e - pl->N : e, ky)) e++;
-                    for (int q = x; q < e; q += SEG) items.push_back(zd::FzItem{kyl, q, std::min(SEG, e - q), 0});
-                    x = e;
-                }
-            };
-            add_range(0, pl->half + 1);
-            add_range(pl->half + 1, pl->N);
-        }
-        std::stable_sort(items.begin(), items.end(), [](const zd::FzItem &a, const zd::FzItem &b) { return a.n > b.n; });
-        pl->n_fzitems = (unsigned) items.size();
-        if (!items.empty()) {
-            PLCHECK(hipMalloc((void **) &pl->d_fzitems, sizeof(zd::FzItem) * items.size()));
-            PLCHECK(hipMemcpy(pl->d_fzitems, items.data(), sizeof(zd::FzItem) * items.size(), hipMemcpyHostToDevice));
-        }
-        int dev = 0;
-        hipGetDevice(&dev);
-        hipDeviceGetAttribute(&pl->ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        if (pl->ncu < 1) pl->ncu = 256;
-    }
-
-    // ---- folded-input slabs (two, for the gen||zfft overlap): enough rows per launch to fill the chip ----
-    {
-        const int64_t row_b = y_bytes_per_row(pl);
-        int64_t slab_b = (int64_t) 3 << 29;  // ~1.5 GB per buffer
-        if (const char *env = tune_env("ZD_SLAB_MB")) slab_b = (int64_t) atoll(env) << 20;
-#ifdef ZD_SLAB_MB_FORCE  // experiment (make variant)
-        slab_b = (int64_t) ZD_SLAB_MB_FORCE << 20;
-#endif
-        int rows = (int) std::max<int64_t>(1, slab_b / row_b);
-        rows     = std::min(rows, pl->Hq);
-        if (zd::pack_is_fields(pl->pack)) {  // whole row blocks
-            rows = std::max(zd::FIELD_RB, rows / zd::FIELD_RB * zd::FIELD_RB);
-            while (pl->Hq % rows) rows -= zd::FIELD_RB;
-        }
-        if (v1) {  // the accepted pairs of a slab: N^2 x 16 B per row, <= ~4 GB
-            const int minr = zd::pack_is_fields(pl->pack) ? zd::FIELD_RB : 1;
-            rows = std::max<int64_t>(minr, std::min<int64_t>(rows, ((int64_t) 4 << 30) / (N * N * 16)));
-            if (zd::pack_is_fields(pl->pack)) rows = rows / zd::FIELD_RB * zd::FIELD_RB;
-        }
-        while (pl->Hq % rows) rows--;
-        pl->slab_rows = rows;
-        pl->overlap   = p->serial_z == 0 && !v1 && !any_path;  // version 1: the streams are sequential in ky
-        // PLT with a table that is interpolated (eig_ppd does not divide into PPD): the (x, y) part of the trilinear lookup is
-        // done once per column of a slab (k_eig_lines) instead of once per mode; one slab of lines, refilled on the generator's
-        // stream in front of every generator launch
-        if (g.qPLT && g.genf_tab && !v1 && eig_ppd % N != 0) {
-            const size_t nb = (size_t) (eig_ppd / 2 + 1) * rows * N * 4 * sizeof(double);
-            if (nb <= ((size_t) 1 << 30)) {
-                PLCHECK(hipMalloc((void **) &pl->d_eiglines, nb));
-                g.eig_lines = pl->d_eiglines;
-                g.eig_rows  = rows;
-            }
-        }
-        if (v1) {
-            pl->v1_block = (int) (N / p->numblock);
-            PLCHECK(hipMalloc((void **) &pl->d_v1streams, sizeof(zd::V1Stream) * (size_t) pl->v1_block));
-            PLCHECK(hipMalloc((void **) &pl->d_v1dev, (size_t) rows * N * N * sizeof(double2)));
-            PLCHECK(hipMalloc((void **) &pl->d_v1err, sizeof(int)));
-            PLCHECK(hipMemset(pl->d_v1err, 0, sizeof(int)));
-            g.v1dev = pl->d_v1dev;
-        }
-        // k_genf is a persistent kernel: a few workgroups per CU pull tiles from a counter (one per launch).  With
-        // the second stream active the grid is kept small enough that a k_zfft workgroup (64 KB LDS, 2 waves/SIMD)
-        // always fits beside the generator's waves on every CU.
-        {
-            int dev = 0, ncu = 256;
-            hipGetDevice(&dev);
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-            int per_cu = pl->overlap ? 3 : 6;
-            if (const char *env = tune_env("ZD_GEN_WGS")) per_cu = atoi(env);
-#ifdef ZD_GEN_WGS_FORCE  // experiment (make variant)
-            if (pl->overlap) per_cu = ZD_GEN_WGS_FORCE;
-#endif
-            pl->gen_max_wgs = std::max(1, per_cu) * std::max(1, ncu);
-            pl->n_tilectr   = 2 * (pl->Hq / rows) + 2;  // per pass parity: the next pass's generator may already run
-            PLCHECK(hipMalloc((void **) &pl->d_tilectr, sizeof(unsigned) * pl->n_tilectr));
-        }
-        // ring size: 1 slab without the overlap, else 2 + what the store (allocated by the caller afterwards) leaves
-        int K = 1;
-        if (pl->overlap) {
-            K = 2;
-            const int nslab = pl->Hq / rows;
-            // Measured (PPD=4096 ZA, 60 slabs ahead): no gain — the generator's resident workgroups take LDS and
-            // registers from k_yfft (128 KB LDS per workgroup at PPD=4096), which slows down by what the z stage gains.
-            // The larger ring therefore stays an experiment: ZD_Y_AHEAD=1 sizes it from free HBM, ZD_Y_SLABS=n fixes it.
-            if (tune_env("ZD_Y_AHEAD") && pl->npass > 1 && nslab > 2) {
-                size_t free_b = 0, total_b = 0;
-                hipMemGetInfo(&free_b, &total_b);
-                const int64_t reserve = zd_plan_exchange_bytes(pl) * (nranks > 1 ? 2 : 1) + ((int64_t) 8 << 30);
-                const int64_t spare   = (int64_t) free_b - reserve;
-                if (spare > 0) K = (int) std::max<int64_t>(2, std::min<int64_t>(nslab, spare / (row_b * rows)));
-            }
-            if (const char *env = tune_env("ZD_Y_SLABS")) K = std::max(2, atoi(env));
-        }
-        pl->d_Y.assign(K, nullptr);
-        for (int i = 0; i < K; i++) PLCHECK(hipMalloc((void **) &pl->d_Y[i], (size_t) row_b * rows));
-        if (pl->overlap) {
-#ifdef ZD_TUNING
-            // A/B (VERDICT r4 #5 i): ZD_CU_SPLIT = n gives the z FFT's stream n CUs of every XCD's 32 and the generator's stream
-            // the other 32 - n (hipExtStreamCreateWithCUMask; CU c of the mask = XCD c % 8, CU c / 8 of it on this part)
-            if (const char *env = tune_env("ZD_CU_SPLIT")) {
-                const int nf = std::max(1, std::min(31, atoi(env)));
-                uint32_t mg[8] = {0}, mf[8] = {0};
-                for (int c = 0; c < 256; c++) ((c / 8) < nf ? mf : mg)[c / 32] |= 1u << (c % 32);
-                PLCHECK(hipExtStreamCreateWithCUMask(&pl->s_gen, 8, mg));
-                PLCHECK(hipExtStreamCreateWithCUMask(&pl->s_fft, 8, mf));
-            } else
-#endif
-            {
-                PLCHECK(hipStreamCreateWithFlags(&pl->s_gen, hipStreamNonBlocking));
-                PLCHECK(hipStreamCreateWithFlags(&pl->s_fft, hipStreamNonBlocking));
-            }
-            PLCHECK(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
-            pl->ev_gen.assign(K, nullptr);
-            pl->ev_fft.assign(K, nullptr);
-            for (int i = 0; i < K; i++) {
-                PLCHECK(hipEventCreateWithFlags(&pl->ev_gen[i], hipEventDisableTiming));
-                PLCHECK(hipEventCreateWithFlags(&pl->ev_fft[i], hipEventDisableTiming));
-            }
-        }
-    }
-    if (any_path) {  // simple [plane][array][y][x] store; tables for the z lines (length L) and the y / x lines (length N): composite
-                     // twiddles for f_NL on the composite grids (fnl_np2), Bluestein tables otherwise
-        if (fnl_np2(p) && fnl_np2_factor_ok(N, R)) {
-            if (upload_twq(pl->N, &pl->d_twr_n) || upload_twq(pl->L, &pl->d_twr_l)) {
-                fprintf(stderr, "zeldovich_hip: composite twiddle tables failed\n");
-                zd_plan_destroy(pl);
-                return 1;
-            }
-        } else if (any_make_tab(pl->L, &pl->tabL, pl->d_any) || any_make_tab(pl->N, &pl->tabN, pl->d_any + 3)) {
-            zd_plan_destroy(pl);
-            return 1;
-        }
-        pl->AL.N         = pl->N;
-        pl->AL.pitch     = pl->N + store_row_pad(pl->N);
-        pl->AL.narray    = pl->narray;
-        pl->store_bytes_ = (int64_t) pl->L * pl->narray * pl->N * pl->AL.pitch * 16;
-        if (nranks > 1) {  // [chunk = peer rank][local plane][array][row slot < 2 Hq][x]: 1 / G of the one-rank store
-            pl->AC           = zd::AnyChunks{pl->N, pl->AL.pitch, pl->narray, nranks, pl->Hq, pl->Zq, 0};
-            pl->AC.chunk     = (long long) pl->Zq * pl->narray * 2 * pl->Hq * pl->AL.pitch;
-            pl->store_bytes_ = (int64_t) nranks * pl->AC.chunk * 16;
-        }
-    }
-#undef PLCHECK
     *out = pl;
     return 0;
+}
+
+static int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
+                          int phi_mode, const cplx *phik, zd_plan **out) {
+    const zd_params pc = zd::canonical(p_in);
+    const int role = phi_mode == 1 ? zd::ROLE_PHI : phik ? zd::ROLE_PHIK : zd::ROLE_MAIN;
+    const bool have_eig = eig != nullptr && eig_ppd > 0;
+    zd_params pa, pb;
+    Route ra, rb;
+    if (role == zd::ROLE_MAIN && zd::plt_dens_split(&pc, nranks) && have_eig && split_routes(&pc, pc.stream_factor, &pa, &pb, &ra, &rb) && ra.ok()
+        && rb.ok()) {
+        zd_plan *A = nullptr, *B = nullptr;
+        bool ok = plan_create_one(&pa, ra, pk, eig, eig_ppd, rank, nranks, role, nullptr, &A) == 0
+                  && plan_create_one(&pb, rb, pk, nullptr, 0, rank, nranks, role, nullptr, &B) == 0;
+        if (ok) ok = zd_store_alloc((void **) &A->d_dens_pass, (size_t) A->Zq * pc.ppd * pc.ppd * sizeof(float)) == hipSuccess;
+        if (ok) {
+            A->dens_sub     = B;
+            A->p            = pc;  // (what the callers read back: ZD_qdensity = 1)
+            A->store_bytes_ = std::max(A->store_bytes_, B->store_bytes_);
+            *out            = A;
+            return 0;
+        }
+        zd_plan_destroy(B);
+        zd_plan_destroy(A);  // the run falls back to the reference arrays (convolution path)
+    }
+    const Route rt = route(&pc, pc.stream_factor, nranks, role, rank, have_eig);
+    if (!rt.ok()) {
+        fprintf(stderr, "zeldovich_hip: %s\n", rt.why);
+        return 1;
+    }
+    return plan_create_one(&pc, rt, pk, eig, eig_ppd, rank, nranks, role, phik, out);
 }
 
 void zd_plan_destroy(zd_plan *pl) {

@@ -1,0 +1,221 @@
+// zd_route.h — where routing lives: zd::route() maps (canonical parameters, stream factor, ranks, role) to the kernel family and the
+// shape of the store that plan creation (zd_capi.cpp plan_create_one) builds and that the choosers (zd_choose_stream_factor,
+// zd_choose_pass_groups) size.  Host only: no HIP call, no allocation; the environment only through tune_env (-DZD_TUNING).
+#pragma once
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+
+#include "../../include/zeldovich_hip.h"
+#include "zd_device.h"
+#include "zd_launch.h"
+
+// Tuning / ablation knobs (environment variables ZD_ABLATE, ZD_PRUNE, ZD_NT, ZD_LAYOUT, ...) exist only in the
+// -DZD_TUNING build (make tuning -> build/libzeldovich_hip_tuning.so, used by scripts/ through ZD_LIB_PATH).
+// The product library never reads the environment: the names do not even reach its binary.  (Global, macro in the product: this
+// header is for zd_capi.cpp alone.)
+#ifdef ZD_TUNING
+static inline const char *tune_env(const char *name) { return getenv(name); }
+#else
+#define tune_env(name) ((const char *) nullptr)
+#endif
+
+namespace zd {
+
+inline bool is_pow2(int64_t n) { return n > 0 && (n & (n - 1)) == 0; }
+
+// Four kernel families:
+//   FAM_POW2           PPD = 2^a: the power-of-two engine (zd_kernels.hip), every store
+//   FAM_COMPOSITE      PPD = 2^a 3^b 5^c 7^d of the kernel table: composite-transform kernels, field stores only (zd_kernels_np2.hip)
+//   FAM_REF_COMPOSITE  ZD_f_NL on such a grid: the reference's arrays, every line through the composite transforms of
+//                      zd_kernels_np2_ref.hip (the second pass keeps the Nyquist modes live, so the Hermitian field stores cannot
+//                      carry it); several ranks split the arrays (AnyChunks)
+//   FAM_CONVOLUTION    any other even PPD — or a composite one with options the composite kernels lack: the reference's arrays, one
+//                      rank, the lines as convolutions on the power-of-two engine (zd_kernels_any.hip); R any divisor of PPD
+enum { FAM_POW2 = 0, FAM_COMPOSITE = 1, FAM_REF_COMPOSITE = 2, FAM_CONVOLUTION = 3 };
+// what a plan is for: the main pass, the first f_NL pass (one array holding phi = D/M), the second (D = PhiK * M)
+enum { ROLE_MAIN = 0, ROLE_PHI = 1, ROLE_PHIK = 2 };
+
+struct Route {
+    int family = FAM_POW2, pack = PACK_NONE, narray = 0, pstep = 1, npass = 1, R = 1, L = 0, Hq = 0, Zq = 0;
+    bool dens = false;       // ZD_qdensity on the six-field ZA store (composite grids)
+    bool dens_only = false;  // ZD_qdensity = 2 there: density planes only: no displacement arrays, no records (src/output.cpp:94,207)
+    bool twr = false;        // reference arrays: the lines use the composite twiddles (else Bluestein tables)
+    // The shape above is filled whatever is refused.  `legal`: family, stream factor, ranks and store take this job — what the
+    // choosers ask; `why`: the first refusal in the order plan creation reports them ("" = none), which may also name an argument of
+    // plan creation alone (eigenmode table, rank index, ZD_Version)
+    bool legal = true;
+    char why[320] = "";
+    bool ok() const { return why[0] == 0; }
+    void refuse(bool routing, const char *fmt, ...) {
+        va_list ap;
+        va_start(ap, fmt);
+        if (!why[0]) vsnprintf(why, sizeof why, fmt, ap);
+        va_end(ap);
+        legal = legal && !routing;
+    }
+};
+
+// ZD_qdensity = 2 (density only): the displacement arrays are never built (src/zeldovich.cpp:303,440), so the eigenmodes of ZD_qPLT
+// never enter — the run IS the ZA density-only run, on every grid and path
+inline zd_params canonical(const zd_params *p) {
+    zd_params c = *p;
+    if (c.qdensity == 2) c.qPLT = c.qPLTrescale = 0;
+    return c;
+}
+
+// a composite PPD whose options (no f_NL, no ZD_qoneslab, store auto / fields) the composite kernels have
+inline bool composite_options(const zd_params *p) {
+    return p->f_NL == 0. && p->qoneslab < 0 && !is_pow2(p->ppd) && np2_supported_ppd((int) p->ppd)
+           && (p->store_mode == ZD_STORE_AUTO || p->store_mode == ZD_STORE_FIELDS);
+}
+// ZD_qdensity = 1 on the composite grids (round 4): the ZA field store carries two more half-space sums — the density D of the two
+// residues of a pass — and the y / x stages add one array, delta_r0 + i delta_r1 (zd_kernels_np2.hip).  The power-of-two grids keep
+// the reference's arrays for ZD_qdensity (their kernels exist).  8640 = 64 * 135 included (tests/test_gpu_baseline_regime.py).
+// ZD_qdensity = 2 (round 5): the same six-field store, the displacement arrays are simply not built and no records are written; the
+// four potentials ride along unused, which still beats the convolution path by ~4x.
+inline bool dens_fields(const zd_params *p) { return (p->qdensity == 1 || p->qdensity == 2) && !p->qPLT && composite_options(p); }
+// PLT with ZD_qdensity = 1 on the composite grids, one rank (round 5): the PLT field store has no density field and its paired
+// generator no registers for a seventh pair of sums, so the density planes come from a second plan — density only, ZA six-field
+// store (dens_only) — at stream factor 2R: its pass j holds the residues j and j + R, i.e. exactly the planes z = j (mod R) of this
+// plan's pass j, in the same delivery order.  It runs at the head of the Z stage on the same store (which the PLT pass then
+// overwrites) and leaves N/R planes of float32 behind.  Before: the ~6x slower convolution path.
+inline bool plt_dens_split(const zd_params *p, int nranks) {
+    return p->qPLT && p->qdensity == 1 && nranks == 1 && composite_options(p) && !tune_env("ZD_NO_DENS_SPLIT");
+}
+
+// reference arrays of a job: density only one (zeldovich.cpp:871-876), PLT four, else two
+inline int ref_arrays(const zd_params *p) { return p->qdensity == 2 ? 1 : (p->qPLT ? 4 : 2); }
+
+// Packed stores (zd_device.h PACK_*) the options ask for: without ZD_qdensity the density field is not transformed.
+inline int pack_mode(const zd_params *p, int R) {
+    if (p->store_mode == ZD_STORE_REFERENCE) return PACK_NONE;
+    if ((p->qdensity != 0 && !dens_fields(p)) || p->f_NL != 0.) return PACK_NONE;
+    if (p->qoneslab >= 0) return PACK_NONE;  // density_variance is then the sum over that one slab (output.cpp:197)
+    {   // The packed stores treat every field as the transform of a REAL field (Hermitian modes) and take
+        // density_variance from sum |D|^2.  That needs every mode with a component on the Nyquist plane |k_i| = N/2 to
+        // be zero: the |k_i| == kmax rule does it when kmax == N/2 (k_cutoff = 1), the spherical cut when k_cutoff >= 1
+        // and CornerModes is off.  Otherwise (e.g. CornerModes with k_cutoff = 2) the reference keeps independent,
+        // non-Hermitian draws there and takes Re/Im of the mixed field (zeldovich.cpp:350-356): reference arrays.
+        const int half = (int) (p->ppd / 2), kmax = (int) ((double) half * (1.0 / p->k_cutoff) + .5);
+        const bool nyquist_dead = kmax == half || (!p->corner_modes && p->k_cutoff >= 1.0);
+        if (!nyquist_dead) return PACK_NONE;
+    }
+    // PLT: the three packed arrays by default; its field store (six half-space sums) only on request — measured slower
+    // (PPD=2048 PLT+rescale 0.553 -> 0.609 s: every array of the y stage needs two potentials, each fetched twice, and the
+    // 148-VGPR PLT generator leaves no room for the z FFT beside it anyway)
+    // (PPD = 8192: the x pass of the packed arrays does not exist — three lines of a row are 1536 threads — so PLT runs on
+    // its field store there, whose ring goes through k_xfft_two; ZA: only the field store has an x kernel that takes them in
+    // sequence, k_xfft_seq)
+    // composite PPD: the composite-transform kernels exist for the field stores only
+    if (p->qPLT) return (p->ppd > 4096 || !is_pow2(p->ppd) || p->store_mode == ZD_STORE_FIELDS) ? PACK_PLTFIELD : PACK_PLT3;
+    if (R < 2) return PACK_NONE;  // the ZA packings carry two z-residues per pass
+    if (p->store_mode == ZD_STORE_PACKED) return p->ppd > 4096 ? PACK_NONE : PACK_ZAPAIR;
+    return PACK_ZAFIELD;
+}
+
+// stream factors the composite (2^a 3^b 5^c 7^d) kernels take: any EVEN divisor of PPD (two residues r, r + R/2 share a ZA pass) — or
+// 1 — whose z lines have a composite transform.  R = 36 gives PPD = 6912 z lines of 192 = 64 * 3 and 18 passes where the powers of two
+// offer 64 (z lines of 108) and 32 passes: the store of a pass must fit, and between 128 GB and 260 GB there was nothing.
+inline bool np2_stream_factor_ok(int64_t N, int R) {
+    return R >= 1 && (R == 1 || R % 2 == 0) && N % R == 0 && np2_supported_zlen((int) (N / R));
+}
+
+// ZD_f_NL on a composite grid goes through the composite transforms where both line lengths — N (x, y; the phi round's z) and N / R
+// (the z lines of a pass) — have one.  One rank: ZD_StoreMode = reference and ZD_qoneslab keep the convolution transforms, as does
+// any stream factor outside fnl_np2_factor_ok.  Several ranks: the arrays split over the ranks (the z lines of a pass must deal out
+// over them too) and nothing else — those configurations are refused with the reason given here (NULL: none).
+inline const char *fnl_multi_refusal(const zd_params *p) {
+    const int64_t N = p->ppd;
+    if (is_pow2(N)) return N > 4096 ? "ZD_f_NL != 0 on several GPUs needs PPD <= 4096 on the powers of two" : nullptr;
+    if (!np2_supported_ppd((int) N) || !refq_supported_len((int) N))
+        return "ZD_f_NL != 0 on several GPUs needs a PPD with composite transforms (2^a 3^b 5^c 7^d of the kernel table); this PPD runs "
+               "its lines as convolutions, on one GPU only";
+    if (p->store_mode == ZD_STORE_REFERENCE)
+        return "ZD_f_NL != 0 with ZD_StoreMode = reference runs the convolution transforms, on one GPU only";
+    if (p->qoneslab >= 0) return "ZD_f_NL != 0 with ZD_qoneslab runs the convolution transforms, on one GPU only";
+    if (tune_env("ZD_NO_NP2_FNL")) return "ZD_NO_NP2_FNL forces the convolution transforms, which run on one GPU only";
+    return nullptr;
+}
+inline bool fnl_np2_factor_ok(const zd_params *p, int R) {
+    return p->f_NL != 0. && !is_pow2(p->ppd) && !fnl_multi_refusal(p) && R >= 1 && p->ppd % R == 0 && refq_supported_len((int) (p->ppd / R));
+}
+
+// the next stream factor a family tries after R, and the shortest z line it takes: the powers of two double, the composite kernels
+// take the even factors (or 1), the reference's arrays any divisor of PPD (their z-residue fold is a plain decimation)
+inline int next_factor(int family, int R) { return family == FAM_POW2 ? 2 * R : family == FAM_COMPOSITE ? (R == 1 ? 2 : R + 2) : R + 1; }
+inline int min_zlen(int family) { return family == FAM_POW2 ? 32 : family == FAM_COMPOSITE ? 12 : 3; }
+
+// R <= 0: no factor given — plan creation's default (the first one whose z lines the composite kernels have, else 1).  rank and
+// have_eig take part in plan creation's refusals only.
+inline Route route(const zd_params *p, int R_given, int nranks, int role, int rank = 0, bool have_eig = true) {
+    Route r;
+    const int64_t N = p->ppd;
+    const int G = nranks < 1 ? 1 : nranks;
+    const bool pow2 = is_pow2(N), main = role == ROLE_MAIN;
+    int R = R_given > 0 ? R_given : 1;
+    bool comp = false;
+    if (!pow2) {
+        int Rg = R_given > 0 ? R_given : 2;
+        for (int c = 2; R_given <= 0 && N / c >= min_zlen(FAM_COMPOSITE); c += 2)
+            if (np2_stream_factor_ok(N, c)) {
+                Rg = c;
+                break;
+            }
+        // the field stores deal row blocks of FIELD_RB rows to every rank
+        comp = np2_supported_ppd((int) N) && main && np2_stream_factor_ok(N, Rg) && pack_is_fields(pack_mode(p, Rg))
+               && (N / 2) % (G * FIELD_RB) == 0;
+        if (comp) R = Rg;
+    }
+    r.twr    = !comp && fnl_np2_factor_ok(p, R);
+    r.family = pow2 ? FAM_POW2 : comp ? FAM_COMPOSITE : r.twr ? FAM_REF_COMPOSITE : FAM_CONVOLUTION;
+    const bool any = !pow2 && !comp;
+    if (pow2 && (N < 32 || N > 16384)) r.refuse(true, "PPD = %lld unsupported (powers of two: 32 ... 16384)", (long long) N);
+    if (p->qPLT && !have_eig) r.refuse(false, "ZD_qPLT set but no eigenmode table given");
+    if (any && nranks > 1 && p->f_NL != 0.) {  // ZD_f_NL on a composite grid, the arrays split over the ranks (AnyChunks)
+        if (const char *why = fnl_multi_refusal(p)) r.refuse(true, "%s", why);
+        else if (!(r.twr && (N / R) % G == 0 && (N / 2) % G == 0))
+            r.refuse(true, "ZD_f_NL on %d ranks at PPD = %lld: stream factor %d has no composite z lines of length PPD / R dividing over the "
+                           "ranks", nranks, (long long) N, R);
+    } else if (any) {
+        if (N % 2 || N < 8 || N > 8192 || nranks != 1 || R < 1 || N % R || N / R < min_zlen(FAM_CONVOLUTION))
+            r.refuse(true, "PPD = %lld (neither 2^a nor a supported 2^a 3^b configuration) runs as convolutions on the power-of-two engine: "
+                           "even PPD in [8, 8192], one rank, ZD_StreamFactor any divisor of PPD (got %d)", (long long) N, R);
+    } else if (comp ? !np2_stream_factor_ok(N, R) : (!is_pow2(R) || N % R || N / R < min_zlen(FAM_POW2) || N / R > 4096)) {
+        r.refuse(true, "stream factor %d invalid for PPD %lld", R, (long long) N);  // (z-FFT kernels exist up to length 4096)
+    }
+    const bool no_split = nranks < 1 || !is_pow2(nranks) || (N / 2) % G || (N / R) % G;
+    if (no_split || rank < 0 || rank >= nranks)
+        r.refuse(no_split, "cannot split PPD %lld (R=%d) over %d ranks (a power of two dividing PPD/2 and PPD/R is required)", (long long) N, R,
+                 nranks);
+    // legacy mt19937 streams, one per yres (power_spectrum.cpp:18-25); the second f_NL pass takes D from PhiK and draws nothing
+    if (p->version != 0 && p->version != 1 && p->version != 2) r.refuse(false, "ZD_Version = %d (1 or 2 expected)", p->version);
+    if (p->version == 1 && role != ROLE_PHIK && (p->numblock <= 0 || N % p->numblock || (N / p->numblock) % G))
+        r.refuse(false, "ZD_Version = 1 needs ZD_NumBlock dividing PPD and PPD/NumBlock streams divisible by the number of ranks (%d)", nranks);
+    // (density only rides on the six-field ZA store of the composite kernels; everywhere else it is one array)
+    r.narray = role == ROLE_PHI ? 1 : (p->qdensity == 2 && !any && dens_fields(p)) ? 2 : ref_arrays(p);
+    if (main && r.narray >= 2 && !any) r.pack = pack_mode(p, R);
+    // the field stores need row blocks of FIELD_RB rows per rank and a z FFT <= 2048; PPD > 4096 has no other store worth using
+    if (pack_is_fields(r.pack) && (((N / 2) / G) % FIELD_RB || N / R > 2048))
+        r.pack = N > 4096 ? PACK_NONE : (r.pack == PACK_PLTFIELD ? PACK_PLT3 : PACK_ZAPAIR);
+    // a 16384-point line fills a workgroup: only the field store's kernels exist (also 8640 = 64 * 135: ZA)
+    if (N > 8192 && r.pack != PACK_ZAFIELD)
+        r.refuse(true, "PPD = %lld runs on the ZA field store only (ZD_StreamFactor >= 16; no ZD_qPLT / ZD_f_NL / ZD_qdensity = 2; "
+                       "ZD_qdensity = 1 on the composite grid 8640 only)", (long long) N);
+    // (launch_xfft_t would say so only after the Z and y stages of the first pass had run)
+    if (r.pack == PACK_NONE && pow2 && (int64_t) r.narray * (N / 16) > 1024)
+        r.refuse(true, "PPD = %lld on the reference's %d arrays (PLT with ZD_qdensity, ZD_f_NL or ZD_StoreMode = reference) has no x pass: the "
+                       "lines of a row are %lld threads", (long long) N, r.narray, (long long) r.narray * (N / 16));
+    if (r.pack != PACK_NONE) r.narray = 3;
+    r.dens      = r.pack == PACK_ZAFIELD && dens_fields(p);
+    r.dens_only = r.dens && p->qdensity == 2;
+    r.pstep     = (r.pack == PACK_ZAPAIR || r.pack == PACK_ZAFIELD) ? 2 : 1;  // the ZA packings deliver two planes per store plane
+    r.npass     = R / r.pstep;
+    r.R         = R;
+    r.L         = (int) (N / R);
+    r.Hq        = (int) (N / 2) / G;
+    r.Zq        = r.L / G;
+    return r;
+}
+
+}  // namespace zd

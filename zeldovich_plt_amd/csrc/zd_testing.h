@@ -8,6 +8,11 @@
 extern "C" {
 #endif
 #pragma GCC visibility push(default)
+/* ---- host hook (no GPU) -------------------------------------- */
+/* the route (zd_route.h) plan creation takes for (p, stream factor R — 0: none given —, nranks), main pass: out[0 .. 11] = family,
+ * pack, narray, pstep, npass, R, L, Hq, Zq, dens, dens_only, composite twiddles; `why` (cap bytes) gets the refusal text, "" if the
+ * route is accepted.  Returns 0 if accepted, 1 if refused */
+int zd_test_route(const zd_params *p, int32_t R, int32_t nranks, int32_t *out, char *why, int64_t cap);
 /* ---- device test hooks (each needs a GPU) -------------------- */
 /* n counter-addressed draws: out[2*i], out[2*i+1] = the two uint64 of mode (kx,ky,kz)[i] */
 int zd_test_draws(int64_t seed, int64_t n, const int32_t *kxyz, uint64_t *out);
