@@ -262,6 +262,7 @@ typedef struct zd_param_strings {
     int32_t version;
     double f_NL, n_s, Omega_M;
     int64_t np;
+    char Pk_measured_filename[1024]; /* ZD_Pk_measured_filename (optional, not in the reference): the CLI writes the band-power table there */
 } zd_param_strings;
 int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s);
 
@@ -280,6 +281,25 @@ void zd_pk_destroy(zd_pk_handle *h);
 /* load_eigmodes: src/zeldovich.cpp:794-830.  Caller frees with zd_free. */
 int zd_load_eigmodes(const char *path, double **eig, int64_t *eig_ppd);
 void zd_free(void *p);
+
+/* ---- band power of the realised modes ---------------------------------------------------------
+ * One sweep over the modes a run generates (no transform, no store) that bins instead of storing; the definition is pinned in
+ * csrc/zd_kernels_pk.hip.  Bin b holds the modes with (b w)^2 <= kx^2 + ky^2 + kz^2 < ((b + 1) w)^2 (signed integer wavenumbers,
+ * w = bin_width >= 1 fundamentals); zd_power_nbins = the number of bins that hold the whole cube (no GPU needed; 0 for invalid
+ * arguments).  The sums run over all ppd^3 wavevectors, Hermitian pairs counted twice, restricted to the modes the zero rule
+ * leaves alive, k = 0 excluded.  Outputs are HOST arrays of nbins >= zd_power_nbins entries:
+ *   count      modes of the bin (exact)            sum_k      sum |k| fundamental
+ *   sum_dens   sum |D(k)|^2                        sum_input  sum zd_pk_power(|k|)  (= <|D|^2>; with ZD_qPk_fix_to_mean |D|^2 itself)
+ *   sum_disp   sum_j |q_j(k)|^2                    sum_vel    sum_j |v_j(k)|^2  (ZA: vnorm^2 sum_disp; PLT: its own field, rescale included)
+ * zd_plan_measure_power measures the rows of this rank (ky = rank mod nranks): the sums of the ranks add up to the whole; a ZD_f_NL
+ * plan measures D = PhiK M of its own PhiK.  The call returns when the sums are in the arrays.  zd_measure_power is the one-call
+ * form on a one-rank plan.  Refused (message, non-zero): configurations whose Nyquist-plane modes stay alive (ZD_CornerModes with
+ * ZD_k_cutoff != 1) and ZD_Version = 1. */
+int64_t zd_power_nbins(int64_t ppd, int32_t bin_width);
+int zd_plan_measure_power(zd_plan *plan, int32_t bin_width, int64_t nbins, int64_t *count, double *sum_k, double *sum_dens,
+                          double *sum_input, double *sum_disp, double *sum_vel, void *hip_stream);
+int zd_measure_power(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t bin_width, int64_t nbins,
+                     int64_t *count, double *sum_k, double *sum_dens, double *sum_input, double *sum_disp, double *sum_vel);
 
 /* ---- diagnostics ------------------------------------------------------------------------------
  * Which kernel variants this process has launched so far, and how often: one line "count<TAB>line<TAB>launcher" per launch

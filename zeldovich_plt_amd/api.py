@@ -66,6 +66,7 @@ class ZdParamStrings(C.Structure):
         ("Pk_sigma_ratio", C.c_double), ("Pk_smooth", C.c_double), ("Pk_powerlaw_index", C.c_double),
         ("qPk_fix_to_mean", C.c_int32), ("version", C.c_int32),
         ("f_NL", C.c_double), ("n_s", C.c_double), ("Omega_M", C.c_double), ("np", C.c_int64),
+        ("Pk_measured_filename", C.c_char * 1024),
     ]
 
 
@@ -80,7 +81,7 @@ EXPORTED_SYMBOLS = [
     "zd_plan_plane_z", "zd_plan_stage_z", "zd_plan_stage_y", "zd_plan_stage_x", "zd_plan_stats", "zd_comm_unique_id", "zd_comm_create", "zd_comm_destroy", "zd_plan_ring_bytes", "zd_plan_run_pass",
     "zd_params_from_file", "zd_pk_create_from_file", "zd_pk_create_powerlaw", "zd_pk_power",
     "zd_pk_sigmaR", "zd_pk_destroy", "zd_load_eigmodes", "zd_free", "zd_comm_abort", "zd_comm_traffic", "zd_choose_pass_groups", "zd_plan_run_passes", "zd_comm_probe", "zd_choose_pass_groups_measured",
-    "zd_dispatch_report",
+    "zd_dispatch_report", "zd_power_nbins", "zd_plan_measure_power", "zd_measure_power",
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
@@ -176,6 +177,10 @@ def _load(path, testing):
     L.zd_load_eigmodes.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(i64)]
     L.zd_free.argtypes = [vp]
     L.zd_free.restype = None
+    L.zd_power_nbins.argtypes = [i64, i32]
+    L.zd_power_nbins.restype = i64
+    L.zd_plan_measure_power.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.zd_measure_power.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i64, vp, vp, vp, vp, vp, vp]
     L.zd_dispatch_report.argtypes = [C.c_char_p, i64]
     L.zd_dispatch_report.restype = i64
     return L
@@ -347,6 +352,49 @@ def generate(params, ps, eig=None, collect=True, loopback=False, testing=False):
     return out
 
 
+POWER_SUMS = ("sum_k", "sum_dens", "sum_input", "sum_disp", "sum_vel")
+
+
+def power_nbins(ppd, bin_width=1):
+    """bins of measure_power: bin b holds (b w)^2 <= kx^2 + ky^2 + kz^2 < ((b + 1) w)^2 (zd_power_nbins; no GPU needed)"""
+    return int(load_library().zd_power_nbins(int(ppd), int(bin_width)))
+
+
+def _power_arrays(ppd, bin_width):
+    nb = power_nbins(ppd, bin_width)
+    if nb <= 0:
+        raise ValueError("measure_power: bin_width must be an integer >= 1")
+    out = {"count": np.zeros(nb, dtype=np.int64)}
+    for name in POWER_SUMS:
+        out[name] = np.zeros(nb, dtype=np.float64)
+    return nb, out, [out[k].ctypes.data for k in ("count",) + POWER_SUMS]
+
+
+def _power_derived(out):
+    """the derived columns: mean |k| of the bin, measured / input band power, modes"""
+    n = out["count"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["k_mean"] = np.where(n > 0, out["sum_k"] / n, np.nan)
+        out["P_measured / P_input"] = np.where(out["sum_input"] > 0, out["sum_dens"] / out["sum_input"], np.nan)
+    out["nmodes"] = n.copy()
+    return out
+
+
+def measure_power(params, ps, eig=None, bin_width=1):
+    """Band power of the modes a run with these parameters realises (zd_measure_power: one sweep on cuda:0 that bins instead of
+    storing; definition in csrc/zd_kernels_pk.hip).  Returns a dict of numpy arrays over the integer |k| shells of width
+    bin_width: count, sum_k, sum_dens, sum_input, sum_disp, sum_vel and the derived k_mean, "P_measured / P_input", nmodes."""
+    L = load_library()
+    nb, out, ptrs = _power_arrays(params.ppd, bin_width)
+    eigp, eig_ppd = (None, 0)
+    if eig is not None:
+        eig = np.ascontiguousarray(eig, dtype=np.float64)
+        eigp, eig_ppd = eig.ctypes.data, eig.shape[0]
+    if L.zd_measure_power(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, int(bin_width), nb, *ptrs):
+        raise RuntimeError("zd_measure_power failed; see stderr")
+    return _power_derived(out)
+
+
 def generate_planes(params, ps, on_plane, eig=None):
     """zd_generate with a per-plane consumer: on_plane(z, records[y, x]) sees a VIEW valid only during the call (like the
     reference's single output buffer); nothing is accumulated here.  Returns the statistics + the number of planes."""
@@ -433,6 +481,13 @@ class Plan:
         if self.L.zd_plan_run_passes(self.h, comm.h if comm is not None else None, first, step, d_store, d_store2, d_records, rec_planes,
                                      cb, None, stream):
             raise RuntimeError("zd_plan_run_passes failed")
+
+    def measure_power(self, bin_width=1, stream=0):
+        """band power of this rank's rows (zd_plan_measure_power): the sums of the ranks add up to the whole"""
+        nb, out, ptrs = _power_arrays(self.params.ppd, bin_width)
+        if self.L.zd_plan_measure_power(self.h, int(bin_width), nb, *ptrs, stream):
+            raise RuntimeError("zd_plan_measure_power failed; see stderr")
+        return _power_derived(out)
 
     def stats(self):
         st = ZdStats()

@@ -212,4 +212,195 @@ __device__ __forceinline__ void cmac(double &ar, double &ai, double c, double dr
     ai = fma(c, di, ai);
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Per-mode arithmetic of the general generator (k_gen) and the eigenmode lookups of k_genf, shared with the band-power sweep
+// (zd_kernels_pk.hip).  Moved out of zd_kernels.hip unchanged.
+
+// PowerSpectrum::power (src/power_spectrum.cpp:225-261) with SplineFunction::val
+// (include/spline_function.h:141-163).  The reference bisects for the segment; here a uniform-cell
+// table over ln k gives a start index and a short forward scan lands on exactly the segment the
+// bisection would return (largest klo with x[klo] <= v, clamped to [0, n-2]).
+template <bool PLAW>
+__device__ __forceinline__ double pk_power(const GenConst &g, double k2) {  // k2 = |k|^2
+    if (k2 <= 0.0) return 0.0;
+    if constexpr (PLAW) {
+        const double k = sqrt(k2);
+        return pow(k, g.powerlaw_index) * exp(-k2 * g.pk_smooth2) * g.pk_norm;
+    } else {
+        const double v = 0.5 * log(k2);  // = log(sqrt(k2)) to 1 ulp
+        int c   = (int) ((v - g.lut_x0) * g.lut_inv_dx);
+        c       = c < 0 ? 0 : (c >= zd::PK_LUT ? zd::PK_LUT - 1 : c);
+        int klo = g.pk_lut[c];
+        const int last = g.pk_n - 2;
+        while (klo < last && g.pk_x[klo + 1] <= v) klo++;
+        const int khi = klo + 1;
+        const double xl = g.pk_x[klo], xh = g.pk_x[khi];
+        const double h = xh - xl;
+        const double a = (xh - v) / h, b = (v - xl) / h;
+        const double val = a * g.pk_y[klo] + b * g.pk_y[khi]
+                           + ((a * a * a - a) * g.pk_y2[klo] + (b * b * b - b) * g.pk_y2[khi]) * (h * h) / 6.0;
+        return exp(val - k2 * g.pk_smooth2) * g.pk_norm;
+    }
+}
+
+// sin and cos of 2*pi*theta for theta in (0,1]: exact octant reduction (theta*8 is exact), then the
+// fdlibm kernel polynomials on [0, pi/4].  cgauss<2> (power_spectrum.cpp:353-356) evaluates
+// cos/sin(fl(2*M_PI*theta)); the two differ by the rounding of that product, ~4e-16 absolute.
+__device__ __forceinline__ void sincos2pi(double theta, double &sn, double &cs) {
+    const double t8 = theta * 8.0;
+    const int q     = (int) t8;
+    const double f  = t8 - (double) q;
+    const int k     = q & 7;
+    const double r  = (k & 1) ? 1.0 - f : f;
+    const double a  = 0.78539816339744830962 * r;  // pi/4 * r
+    const double z  = a * a;
+    // __kernel_sin / __kernel_cos coefficients (fdlibm k_sin.c, k_cos.c)
+    const double sp = -1.66666666666666324348e-01 + z * (8.33333333332248946124e-03 + z * (-1.98412698298579493134e-04
+                      + z * (2.75573137070700676789e-06 + z * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10))));
+    const double s0 = a + a * z * sp;
+    const double cp = 4.16666666666666019037e-02 + z * (-1.38888888888741095749e-03 + z * (2.48015872894767294178e-05
+                      + z * (-2.75573143513906633035e-07 + z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11))));
+    const double c0 = 1.0 - (0.5 * z - z * z * cp);
+    const bool swap = ((k + 1) & 2) != 0;  // k = 1,2,5,6
+    const double sv = swap ? c0 : s0, cv = swap ? s0 : c0;
+    sn = (k >= 4) ? -sv : sv;                      // k = 4..7: sin < 0
+    cs = (k >= 2 && k <= 5) ? -cv : cv;            // k = 2..5: cos < 0
+}
+
+// cgauss<2> (power_spectrum.cpp:338-359) given P(k) and the two raw draws
+__device__ __forceinline__ void gauss_from_pk(const GenConst &g, double Pk, uint64_t r1, uint64_t r2, double &dr,
+                                              double &di) {
+    double R           = zdpcg::u01(r1);
+    const double theta = zdpcg::u01(r2);
+    if ZD_TUNE(g.ablate & 2) {
+        dr = R * Pk;
+        di = theta * Pk;
+        return;
+    }
+    if (!g.fixed_power)
+        R = sqrt(-Pk * log(R));
+    else
+        R = sqrt(Pk);
+    double sn, cs;
+    sincos2pi(theta, sn, cs);
+    dr = R * cs;
+    di = R * sn;
+}
+template <bool PLAW>
+__device__ __forceinline__ void gauss_mode(const GenConst &g, double k2, uint64_t r1, uint64_t r2, double &dr,
+                                           double &di) {
+    gauss_from_pk(g, ZD_TUNE(g.ablate & 1) ? 1e-9 * k2 : pk_power<PLAW>(g, k2), r1, r2, dr, di);
+}
+
+__device__ __forceinline__ void get_eigenmode_dev(const GenConst &g, int kx, int ky, int kz, const EigAxis &ax,
+                                                  const EigAxis &ay, const EigAxis &az, double (&out)[4]) {
+    const int ep = (int) g.eig_ppd, halfppd = ep / 2 + 1;
+    const double k2 = (double) (kx * kx + ky * ky + kz * kz);
+    double eh[4];
+    const double2 *E = reinterpret_cast<const double2 *>(g.eig);  // [x][y][z][4] doubles = 2 double2 per entry
+    if (ep % g.N == 0) {
+        const int i = ((ax.l * ep + ay.l) * halfppd + az.l) * 2;
+        const double2 q0 = E[i], q1 = E[i + 1];
+        eh[0] = q0.x;
+        eh[1] = q0.y;
+        eh[2] = q1.x;
+        eh[3] = q1.y;
+    } else {
+        // trilinear weights and corners in the reference's order f[0..7] = (x l/h, y l/h, z l/h) with z
+        // fastest; accumulated left to right like the single expression of zeldovich.cpp:218-225.
+        // Corners with zero weight are not read (the reference reads them: same value unless non-finite).
+        eh[0] = eh[1] = eh[2] = eh[3] = 0.0;
+#pragma unroll 2
+        for (int c = 0; c < 8; c++) {
+            const double wx = (c & 4) ? ax.f : 1 - ax.f, wy = (c & 2) ? ay.f : 1 - ay.f, wz = (c & 1) ? az.f : 1 - az.f;
+            const double wgt = wx * wy * wz;
+            if (wgt != 0) {
+                const int cx = (c & 4) ? ax.h : ax.l, cy = (c & 2) ? ay.h : ay.l, cz = (c & 1) ? az.h : az.l;
+                const int i  = ((cx * ep + cy) * halfppd + cz) * 2;
+                const double2 q0 = E[i], q1 = E[i + 1];
+                eh[0] += wgt * q0.x;
+                eh[1] += wgt * q0.y;
+                eh[2] += wgt * q1.x;
+                eh[3] += wgt * q1.y;
+            }
+        }
+    }
+    eh[2] *= (kz < 0 ? -1.0 : 1.0);  // copysign(1, kz) for an int: kz = 0 -> +1
+    const double imag = 1.0 / sqrt(eh[0] * eh[0] + eh[1] * eh[1] + eh[2] * eh[2]);
+    eh[0] *= imag;  // the reference divides each component (zeldovich.cpp:257-259): <= 1 ulp apart
+    eh[1] *= imag;
+    eh[2] *= imag;
+    double norm = k2 / (kx * eh[0] + ky * eh[1] + kz * eh[2]);
+    if (k2 == 0.0 || !isfinite(norm)) norm = 0.0;
+    out[0] = norm * eh[0];
+    out[1] = norm * eh[1];
+    out[2] = norm * eh[2];
+    out[3] = eh[3];
+}
+
+// Tail of the k_genf eigenmode lookups: from the blended (un-normalised) table entry eh = (e_x, e_y, e_z, lambda) of |kz| to the
+// coefficient of the displacement, out[j] = s_j = e_j k^2 / (k.e) x fundamental / k^2 = e_j / ((k.e) fundamental) (round 5: neither
+// |e| nor k^2 enters — the reference normalises e, src/zeldovich.cpp:255-262, forms e k^2 / (k.e) and LoadPlane multiplies by
+// fundamental / k^2, :428-434; one reciprocal instead of an inverse square root with two Newton steps and two reciprocals: 25 of a
+// PLT mode's ~350 instructions); k.e = 0 or not finite -> 0 as there (:262-263; k = 0 does not occur: ky >= 1); out[3] = lambda
+__device__ __forceinline__ void eig_coeff_tail(double fundamental, int kx, int ky, int kz, double (&eh)[4], double (&out)[4]) {
+    eh[2] *= (kz < 0 ? -1.0 : 1.0);
+    const double dot = kx * eh[0] + ky * eh[1] + kz * eh[2];
+    double inv = frcp(dot * fundamental);
+    if (!isfinite(inv)) inv = 0.0;
+    out[0] = inv * eh[0];
+    out[1] = inv * eh[1];
+    out[2] = inv * eh[2];
+    out[3] = eh[3];
+}
+
+// get_eigenmode for k_genf: the (x, y) part of the lookup — table offsets of the 4 corner columns and the products
+// w_x w_y — depends on the thread's kx and the row's ky only and is prepared once per tile; per mode remain the two
+// z corners, 1/|e| by rsq + Newton and k^2/(k.e) by reciprocal (get_eigenmode_dev: sqrt + two divisions).
+// Accumulation order and weight association are those of get_eigenmode_dev / zeldovich.cpp:218-225.
+struct EigXY {
+    int base[4];   // ((cx*ep + cy)*halfppd)*2 in double2 units, corners (l,l), (l,h), (h,l), (h,h)
+    double w[4];   // w_x * w_y
+};
+__device__ __forceinline__ EigXY eig_xy(const GenConst &g, const EigAxis &ax, const EigAxis &ay) {
+    const int ep = (int) g.eig_ppd, halfppd = ep / 2 + 1;
+    EigXY q;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int cx = (c & 2) ? ax.h : ax.l, cy = (c & 1) ? ay.h : ay.l;
+        q.base[c] = ((cx * ep + cy) * halfppd) * 2;
+        q.w[c]    = ((c & 2) ? ax.f : 1 - ax.f) * ((c & 1) ? ay.f : 1 - ay.f);
+    }
+    return q;
+}
+__device__ __forceinline__ void eigenmode_fast(const GenConst &g, int kx, int ky, int kz, const EigXY &q, const EigAxis &az,
+                                               double (&out)[4]) {
+    const double fundamental = g.fundamental;
+    const double2 *E = reinterpret_cast<const double2 *>(g.eig);
+    double eh[4];
+    if ((int) g.eig_ppd % g.N == 0) {
+        const int i = q.base[0] + az.l * 2;
+        const double2 q0 = E[i], q1 = E[i + 1];
+        eh[0] = q0.x;
+        eh[1] = q0.y;
+        eh[2] = q1.x;
+        eh[3] = q1.y;
+    } else {
+        eh[0] = eh[1] = eh[2] = eh[3] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            const double wgt = q.w[c >> 1] * ((c & 1) ? az.f : 1 - az.f);
+            if (wgt != 0) {
+                const int i = q.base[c >> 1] + ((c & 1) ? az.h : az.l) * 2;
+                const double2 q0 = E[i], q1 = E[i + 1];
+                eh[0] += wgt * q0.x;
+                eh[1] += wgt * q0.y;
+                eh[2] += wgt * q1.x;
+                eh[3] += wgt * q1.y;
+            }
+        }
+    }
+    eig_coeff_tail(fundamental, kx, ky, kz, eh, out);
+}
 }  // namespace zdgen

@@ -515,6 +515,16 @@ static int read_statements(const char *path, HeaderState &H, int depth) {
     return 0;
 }
 
+// bins of the band-power measurement (zd_kernels_pk.hip): bin b = (b w)^2 <= |k|^2 < ((b + 1) w)^2, |k|^2 <= 3 (ppd/2)^2
+int64_t zd_power_nbins(int64_t ppd, int32_t bin_width) {
+    if (ppd < 2 || ppd > ZD_MAX_PPD || bin_width < 1) return 0;
+    const int64_t h = ppd / 2, k2 = 3 * h * h;
+    int64_t r = (int64_t) sqrt((double) k2);
+    while (r * r > k2) r--;
+    while ((r + 1) * (r + 1) <= k2) r++;
+    return r / bin_width + 1;
+}
+
 int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     HeaderState H;
     if (read_statements(path, H, 0)) return 1;
@@ -616,6 +626,7 @@ int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     I("ZD_StreamFactor", p->stream_factor);
     I("ZD_NumGPU", p->ngpu);  // GPUs of this node to drive (default: 1)
     I("ZD_ExchangePlanes", p->exchange_planes);
+    S("ZD_Pk_measured_filename", s->Pk_measured_filename, sizeof(s->Pk_measured_filename));  // band-power table after the run (empty: none)
     I("ZD_PassGroups", p->pass_groups);  // independent groups of GPUs, residue passes dealt round-robin (0: automatic)
     (void) have_cpd;
     p->cpd = cpd;

@@ -19,6 +19,8 @@
 #include <filesystem>
 #include <map>
 #include <string>
+#include <vector>
+#include <algorithm>
 
 #include "../../include/zeldovich_hip.h"
 
@@ -100,6 +102,30 @@ static void setup_output_dir(const fs::path &dir) {
 
 static double cube(double a) { return a == 0.0 ? 0.0 : a * a * a; }
 
+// ZD_Pk_measured_filename: band power of the realised modes (zd_measure_power), one line per non-empty |k| shell
+static int write_measured_power(const char *path, const zd_params &p, const zd_pk &pk, const double *eig, int64_t eig_ppd) {
+    const int64_t nb = zd_power_nbins(p.ppd, 1);
+    std::vector<int64_t> count(nb);
+    std::vector<double> sk(nb), sd(nb), si(nb), sq(nb), sv(nb);
+    if (zd_measure_power(&p, &pk, eig, eig_ppd, 1, nb, count.data(), sk.data(), sd.data(), si.data(), sq.data(), sv.data())) return 1;
+    FILE *f = fopen(path, "w");
+    if (!f) {
+        fprintf(stderr, "Could not open band-power file \"%s\"\n", path);
+        return 1;
+    }
+    fprintf(f, "# k_mean count P_measured P_input disp_power vel_power\n");
+    double worst = 0.0;
+    for (int64_t b = 0; b < nb; b++) {
+        if (count[b] == 0) continue;
+        const double n = (double) count[b];
+        fprintf(f, "%.17g %lld %.17g %.17g %.17g %.17g\n", sk[b] / n, (long long) count[b], sd[b] / n, si[b] / n, sq[b] / n, sv[b] / n);
+        if (si[b] > 0) worst = std::max(worst, fabs(sd[b] / si[b] - 1.0) * sqrt(n));
+    }
+    fclose(f);
+    fprintf(stderr, "Measured band power written to %s: worst |P_measured / P_input - 1| sqrt(count) over the bins is %g\n", path, worst);
+    return 0;
+}
+
 int main(int argc, char *argv[]) {
     if (argc != 2) {
         fprintf(stderr, "Usage: %s param_file\n", argv[0]);
@@ -177,6 +203,7 @@ int main(int argc, char *argv[]) {
                 "For Abacus' 2LPT implementation to work (assuming FINISH_WAIT_RADIUS = 1),\n\tthis implies a maximum CPD of %d\n",
                 (int) (p.boxsize / (2 * fabs(st.max_disp[2]))));
     }
+    if (s.Pk_measured_filename[0] && write_measured_power(s.Pk_measured_filename, p, pk, eig, eig_ppd)) exit(1);
     w.close_all();
     fprintf(stderr, "WriteParticlesSlab took %.3g sec to write %.3g MB ==> %.3g MB/sec\n", w.seconds,
             w.bytes_written / 1e6, w.bytes_written / 1e6 / (w.seconds > 0 ? w.seconds : 1e-9));
