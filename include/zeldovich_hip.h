@@ -72,6 +72,14 @@ typedef struct zd_params {
                             * one GPU per group while the job has at least ngpu passes (2 and 4 GPUs at PPD = 4096: no
                             * exchange at all, where a pairwise exchange would be bound by ONE xGMI link), else one group
                             * of all GPUs (the all-to-all of 8 GPUs, every link of the mesh busy) */
+    /* --- second-order Lagrangian perturbation theory (not in the reference; definition: csrc/zd_kernels_lpt2.hip) ---
+     * q2LPT = 1 (ZD_q2LPT): displacement = psi1 + psi2, velocity = vnorm psi1 + lpt2_f2 psi2, with psi2 the Fourier-space 2LPT
+     * displacement of the ZA field, scaled by lpt2_ratio = D2 / D1^2.  The two coefficients (ZD_2LPT_D2, ZD_2LPT_f2): 0 = the
+     * values of the ZD_f_cluster background, -(2 vnorm + 1) / (6 vnorm + 1) (-3/7 at f_cluster = 1) and 2 vnorm.
+     * ZD_Version 2, one GPU, PPD a power of two in [32, 2048]; not with ZD_qPLT, ZD_f_NL, ZD_qdensity, or ZD_CornerModes
+     * together with ZD_k_cutoff != 1 */
+    int32_t q2LPT;
+    double lpt2_ratio, lpt2_f2;
 } zd_params;
 
 /* zd_params.store_mode */
@@ -294,7 +302,7 @@ void zd_free(void *p);
  * zd_plan_measure_power measures the rows of this rank (ky = rank mod nranks): the sums of the ranks add up to the whole; a ZD_f_NL
  * plan measures D = PhiK M of its own PhiK.  The call returns when the sums are in the arrays.  zd_measure_power is the one-call
  * form on a one-rank plan.  Refused (message, non-zero): configurations whose Nyquist-plane modes stay alive (ZD_CornerModes with
- * ZD_k_cutoff != 1) and ZD_Version = 1. */
+ * ZD_k_cutoff != 1), ZD_Version = 1 and q2LPT plans (the sweep regenerates the first-order modes only). */
 int64_t zd_power_nbins(int64_t ppd, int32_t bin_width);
 int zd_plan_measure_power(zd_plan *plan, int32_t bin_width, int64_t nbins, int64_t *count, double *sum_k, double *sum_dens,
                           double *sum_input, double *sum_disp, double *sum_vel, void *hip_stream);

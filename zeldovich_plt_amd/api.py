@@ -36,6 +36,7 @@ class ZdParams(C.Structure):
         ("store_mode", C.c_int32), ("serial_z", C.c_int32), ("ngpu", C.c_int32), ("exchange_planes", C.c_int32),
         ("f_NL", C.c_double), ("n_s", C.c_double), ("Omega_M", C.c_double),
         ("version", C.c_int32), ("pass_groups", C.c_int32),
+        ("q2LPT", C.c_int32), ("lpt2_ratio", C.c_double), ("lpt2_f2", C.c_double),
     ]
 
 
@@ -85,7 +86,7 @@ EXPORTED_SYMBOLS = [
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
-                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route"]
+                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route", "zd_test_lpt2_coefficients"]
 STORE_MODES = {"auto": 0, "reference": 1, "packed": 2, "fields": 3}  # zd_params.store_mode (ZD_STORE_*)
 
 _lib = None
@@ -134,6 +135,8 @@ def _load(path, testing):
         L.zd_test_ycols.argtypes = [i32, i32, i32, i32, i32, vp, vp]
         L.zd_test_poison.argtypes = [C.c_int]
         L.zd_test_poison.restype = None
+        L.zd_test_lpt2_coefficients.argtypes = [C.POINTER(ZdParams), vp]
+        L.zd_test_lpt2_coefficients.restype = None
     L.zd_choose_stream_factor.argtypes = [C.POINTER(ZdParams), C.c_int, i64]
     L.zd_choose_pass_groups.argtypes = [C.POINTER(ZdParams), C.c_int, i64, C.POINTER(i32), C.POINTER(i32)]
     L.zd_plan_create.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, C.c_int, C.c_int, C.POINTER(vp)]
@@ -204,9 +207,10 @@ def make_params(ppd, numblock=2, boxsize=720.0, seed=12346, k_cutoff=1.0, qPLT=0
                 PLT_target_z=0.0, z_initial=49.0, f_cluster=1.0, icformat="RVdoubleZel", qdensity=0,
                 qoneslab=-1, qonemode=0, one_mode=(0, 0, 0), corner_modes=0, cpd=None, stream_factor=0,
                 profile=0, f_NL=0.0, n_s=1.0, Omega_M=1.0, store_mode="auto", serial_z=0, ngpu=0, exchange_planes=0,
-                version=2, pass_groups=0):
+                version=2, pass_groups=0, q2LPT=0, lpt2_ratio=0.0, lpt2_f2=0.0):
     """Parameters with the derived quantities of Parameters::setup (src/parameters.cpp:172-174); version = 1 (legacy
-    mt19937 streams) adjusts NumBlock by k_cutoff as the reader does (src/parameters.cpp:129-141)."""
+    mt19937 streams) adjusts NumBlock by k_cutoff as the reader does (src/parameters.cpp:129-141).  q2LPT = 1 adds the
+    second-order displacements (csrc/zd_kernels_lpt2.hip); lpt2_ratio = D2 / D1^2 and lpt2_f2: 0 = the f_cluster background's."""
     p = ZdParams()
     p.ppd = ppd
     if version == 1 and k_cutoff != 1.0:
@@ -238,6 +242,7 @@ def make_params(ppd, numblock=2, boxsize=720.0, seed=12346, k_cutoff=1.0, qPLT=0
     p.exchange_planes = exchange_planes
     p.pass_groups = pass_groups
     p.f_NL, p.n_s, p.Omega_M = f_NL, n_s, Omega_M
+    p.q2LPT, p.lpt2_ratio, p.lpt2_f2 = q2LPT, lpt2_ratio, lpt2_f2
     return p
 
 

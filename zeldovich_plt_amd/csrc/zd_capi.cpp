@@ -368,6 +368,11 @@ int zd_test_route(const zd_params *p_in, int32_t R, int32_t nranks, int32_t *out
     if (why && cap > 0) snprintf(why, (size_t) cap, "%s", rt.why);
     return rt.ok() ? 0 : 1;
 }
+void zd_test_lpt2_coefficients(const zd_params *p, double *out) {
+    out[0] = zd::lpt2_alpha(p);
+    out[1] = zd::lpt2_ratio(p);
+    out[2] = zd::lpt2_f2(p);
+}
 #endif
 
 // ZD_f_NL on a composite grid, several ranks: bytes per rank of the two-slot exchange ring of a store with `narray` arrays and Zq
@@ -386,6 +391,11 @@ static int64_t fnl_phi_bytes(const zd_params *p) {
     const int64_t N = p->ppd;
     return (route(p, 1, 1, zd::ROLE_PHI).twr ? N / 2 : N) * N * (N + store_row_pad(N)) * 16;
 }
+
+// ZD_q2LPT memory: the source S(k) (half-space rows, PhiK's layout) stays beside every pass's store; the second-order round before it
+// peaks at its one-array store (every plane, self and twin slots) + the real N^3 accumulator, which S(k) then replaces
+static int64_t lpt2_sk_bytes(int64_t N) { return (N / 2) * N * N * 16; }
+static int64_t lpt2_round_bytes(int64_t N) { return N * N * (N + store_row_pad(N)) * 16 + N * N * N * 8; }
 
 // The two halves of a PLT + density run (zd_route.h plt_dens_split) at the PLT half's stream factor R (<= 0: plan creation's
 // default), and whether their shapes fit together: the PLT half on its field store, the density half density-only with the same
@@ -409,6 +419,8 @@ static int choose_stream_factor_one(const zd_params *p, int nranks, int64_t budg
     const int own = is_pow2(N) ? zd::FAM_POW2 : zd::FAM_COMPOSITE;
     // ZA without density: two residues share a pass, so R = 2 is preferred over R = 1 whenever the z FFT is long enough
     const Route r2 = route(p, 2, nranks, zd::ROLE_MAIN);
+    if (p->q2LPT && lpt2_round_bytes(N) > budget_bytes) return -1;
+    const int64_t lpt2_resident = p->q2LPT ? lpt2_sk_bytes(N) : 0;
     for (int R = r2.legal && r2.pstep == 2 ? 2 : 1; N / R >= zd::min_zlen(own); R = zd::next_factor(own, R)) {
         const Route rt = route(p, R, nranks, zd::ROLE_MAIN);
         if (!rt.legal || rt.family != own) continue;
@@ -417,7 +429,7 @@ static int choose_stream_factor_one(const zd_params *p, int nranks, int64_t budg
         if (nranks > 1) store += std::min<int64_t>(store, (int64_t) 9 << 30);  // + the two-slot exchange ring (zd_multi.cpp), not a second store
         if (zd::pack_is_fields(zd::pack_mode(p, R)))  // + the y -> x ring (3 arrays; 4 with the density array); priced like the store
             store += (int64_t) field_ring_planes(N, rt.Zq) * (zd::dens_fields(p) ? 4 : 3) * plane_b;
-        if (store <= budget_bytes) return R;
+        if (store + lpt2_resident <= budget_bytes) return R;
     }
     if (own == zd::FAM_POW2) return -1;
     // Reference arrays.  ZD_f_NL: PhiK stays beside every pass's store, and the phi round before it holds PhiK and the phi planes —
@@ -471,6 +483,10 @@ int zd_choose_pass_groups(const zd_params *p_in, int ngpu, int64_t budget_bytes,
     const zd_params pc = zd::canonical(p_in), *p = &pc;
     const int64_t N = p->ppd;
     if (ngpu < 1) ngpu = 1;
+    if (const char *why = zd::lpt2_refusal(p, ngpu)) {  // (pass groups included: every GPU would run the second-order round)
+        fprintf(stderr, "zeldovich_hip: %s\n", why);
+        return 1;
+    }
     int g = p->pass_groups;
     if (g < 0 || (g > 0 && ngpu % g)) {
         fprintf(stderr, "zeldovich_hip: ZD_PassGroups = %d does not divide ZD_NumGPU = %d\n", g, ngpu);
@@ -589,7 +605,8 @@ static int any_lines(const zd_plan *pl, void *data, long long pitch, long long n
     return zd::launch_any_lines(pl->tabN, data, pitch, nlines, st);
 }
 
-// phi_mode 1: first f_NL pass (one array holding phi = D/M); phik != NULL: second pass (D = phik * M)
+// phi_mode 1: first f_NL pass (one array holding phi = D/M); phik != NULL: second pass (D = phik * M).  ZD_q2LPT: phi_mode 2 = the
+// plan of the second-order round's gradient passes; phik != NULL with phi_mode 0 = the final pass, phik holding the source S(k)
 static int plan_create_ex(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
                           int phi_mode, const cplx *phik, zd_plan **out);
 
@@ -661,6 +678,67 @@ static int make_phik(const zd_params *p, const zd_pk *pk, cplx **d_phik) {
     return frc;
 }
 
+// ZD_q2LPT: the second-order round (definition and shape: zd_kernels_lpt2.hip), run once; *d_sk = S(k)[ky][kz][x] for the half-space
+// rows, already scaled by N^-3 (owned by the caller).  Four gradient passes over one one-array store — generator, z and y stages of
+// the plan, then the x lines into the real accumulator — and the forward transforms of the f_NL phi round.  The accumulator is freed
+// before S(k) is allocated: the peak is lpt2_round_bytes.
+static int make_lpt2_source(const zd_params *p, const zd_pk *pk, cplx **d_sk) {
+    const int64_t N  = p->ppd;
+    zd_params pp     = *p;
+    pp.stream_factor = 1;   // the forward z transform needs every plane of a row
+    pp.qoneslab      = -1;  // (the source needs the whole field whatever is delivered)
+    zd_plan *ph      = nullptr;
+    *d_sk            = nullptr;
+    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 2, nullptr, &ph)) return 1;
+    void *d_grad = nullptr, *d_acc = nullptr;
+    int frc      = 1;
+    do {
+        if (zd_store_alloc(&d_grad, (size_t) zd_plan_exchange_bytes(ph)) != hipSuccess
+            || zd_store_alloc(&d_acc, (size_t) N * N * N * sizeof(double)) != hipSuccess) {
+            fprintf(stderr, "zeldovich_hip: ZD_q2LPT needs %.1f GB of HBM for the second-order round at PPD %lld\n",
+                    lpt2_round_bytes(N) / 1e9, (long long) N);
+            break;
+        }
+        int pass = 1;
+        for (; pass <= 4; pass++) {
+            ph->g.lpt2 = pass;
+            if (zd_plan_stage_z(ph, 0, d_grad, 0) || zd_plan_stage_y(ph, d_grad, 0)) break;
+            if (zd::launch_lpt2_xsrc(ph->S, pass, ph->d_twN, d_grad, (double *) d_acc, (int) N, 0)) break;
+        }
+        if (pass <= 4) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        hipFree(d_acc);
+        d_acc = nullptr;
+        if (zd_store_alloc((void **) d_sk, (size_t) lpt2_sk_bytes(N)) != hipSuccess) {
+            fprintf(stderr, "zeldovich_hip: ZD_q2LPT needs %.1f GB of HBM for the second-order source at PPD %lld\n",
+                    lpt2_sk_bytes(N) / 1e9, (long long) N);
+            break;
+        }
+        int lN = 0;
+        while ((1 << lN) < (int) N) lN++;
+        if (zd::launch_fnl_stage(1, ph->S, 0.0, ph->d_twN, d_grad, nullptr, (int) N, lN, 0)) break;
+        if (zd::launch_fnl_stage(2, ph->S, 0.0, ph->d_twN, d_grad, *d_sk, (int) N, lN, 0)) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        frc = 0;
+    } while (0);
+    hipFree(d_acc);
+    hipFree(d_grad);
+    zd_plan_destroy(ph);
+    if (frc) {
+        hipFree(*d_sk);
+        *d_sk = nullptr;
+    }
+    return frc;
+}
+// a ZD_q2LPT job the route takes for this call (the refusal printed otherwise), asked BEFORE the second-order round is run
+static int lpt2_route_check(const zd_params *p, int nranks, int rank) {
+    const zd_params pc = zd::canonical(p);
+    const Route rt = route(&pc, pc.stream_factor, nranks, zd::ROLE_MAIN, rank, true);
+    if (rt.ok()) return 0;
+    fprintf(stderr, "zeldovich_hip: %s\n", rt.why);
+    return 1;
+}
+
 static zd::StoreLayout layout_for_chunks(const zd_plan *pl, int chunk_planes);
 static zd::AnyChunks any_chunks(const zd_plan *pl, int chunk_planes);
 
@@ -719,6 +797,16 @@ int zd_plan_phi_zfwd(zd_plan *pl, void *d_store, void *d_phik, void *hip_stream)
 
 int zd_plan_create(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
                    zd_plan **out) {
+    if (p->q2LPT) {  // the second-order round runs here, once; the plan owns S(k) and its Z stages read it beside their draws
+        cplx *d_sk = nullptr;
+        if (lpt2_route_check(p, nranks, rank) || make_lpt2_source(p, pk, &d_sk)) return 1;
+        if (plan_create_ex(p, pk, eig, eig_ppd, rank, nranks, 0, d_sk, out)) {
+            hipFree(d_sk);
+            return 1;
+        }
+        (*out)->d_phik_owned = d_sk;
+        return 0;
+    }
     if (p->f_NL == 0.) return plan_create_ex(p, pk, eig, eig_ppd, rank, nranks, 0, nullptr, out);
     // ZD_f_NL: the phi round runs here, once; the plan owns PhiK and its Z stages read D = PhiK * M
     if (nranks != 1) {
@@ -784,7 +872,7 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
             zdpcg::make_bit_table(b);
             return b;
         }();
-        if (zdk_upload_bit_table(&bt) != 0 || zdk_upload_bit_table_fz(&bt) != 0) {
+        if (zdk_upload_bit_table(&bt) != 0 || zdk_upload_bit_table_fz(&bt) != 0 || zdk_upload_bit_table_lpt2(&bt) != 0) {
             fprintf(stderr, "zeldovich_hip: uploading the RNG jump table failed\n");
             return 1;
         }
@@ -911,6 +999,9 @@ static void plan_zstage_jobs(zd_plan *pl) {
         add(zd::JOB_B_TWIN, 1, 1, 0);
         add(zd::JOB_D_SELF, 2, 0, 0);
         add(zd::JOB_D_TWIN, 2, 1, 0);
+    } else if (pl->narray == 1 && pl->g.lpt2) {  // second-order round: two gradient fields as one array (zd_kernels_lpt2.hip)
+        add(zd::JOB_G2_SELF, 0, 0, 0);
+        add(zd::JOB_G2_TWIN, 0, 1, 0);
     } else if (pl->narray == 1) {
         add(zd::JOB_DENS, 0, 0, 0);
     } else {
@@ -930,7 +1021,7 @@ static void plan_zstage_jobs(zd_plan *pl) {
 static int plan_block_layout(zd_plan *pl, bool v1) {
     const zd_params *p = &pl->p;
     zd::GenConst &g = pl->g;
-    const bool main = !g.gen_phi && !g.phik;
+    const bool main = !g.gen_phi && !g.phik && !(g.lpt2 >= 1 && g.lpt2 <= 4);  // (the second-order round's x lines read every column too)
     zd::StoreLayout &S = pl->S;
     S.N      = pl->N;
     S.half   = pl->half;
@@ -992,7 +1083,8 @@ static int plan_block_layout(zd_plan *pl, bool v1) {
     pl->ec.recsize  = record_size(p->icformat);
     pl->ec.qPLT     = p->qPLT;
     pl->ec.qdensity = p->qdensity;
-    pl->ec.vnorm    = p->qPLT ? 1.0 : (sqrt(1. + 24 * p->f_cluster) - 1) * .25;  // output.cpp:78-82
+    // (ZD_q2LPT: arrays 2, 3 hold the velocity field alpha psi1 + f2 psi2 as PLT's hold its own)
+    pl->ec.vnorm    = (p->qPLT || p->q2LPT) ? 1.0 : (sqrt(1. + 24 * p->f_cluster) - 1) * .25;  // output.cpp:78-82
     pl->ec.pack     = pl->pack == zd::PACK_PLTFIELD ? zd::PACK_PLT3 : pl->pack;  // the y stage builds the PLT3 arrays in the ring
     pl->ec.z_pair   = pl->R / 2;
     pl->ec.xdead_lo = 1;  // (none; set below for the field stores' ring)
@@ -1239,7 +1331,7 @@ static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk,
     pl->L         = rt.L;
     pl->Hq        = rt.Hq;
     pl->Zq        = rt.Zq;
-    const bool v1 = p->version == 1 && phik == nullptr;  // (the second f_NL pass takes D from PhiK and draws nothing)
+    const bool v1 = p->version == 1 && phik == nullptr && !p->q2LPT;  // (the second f_NL pass takes D from PhiK and draws nothing)
     // ---- generator constants (zeldovich.cpp:299-320, 350) ----
     zd::GenConst &g = pl->g;
     memset(&g, 0, sizeof(g));
@@ -1279,7 +1371,15 @@ static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk,
     }
     g.eig_ppd = eig_ppd;
     g.gen_phi = role == zd::ROLE_PHI;
-    g.phik    = phik;
+    g.phik    = p->q2LPT ? nullptr : phik;
+    if (role == zd::ROLE_LPT2_GRAD) g.lpt2 = 1;  // (make_lpt2_source sets the pass in front of every Z stage)
+    if (role == zd::ROLE_MAIN && p->q2LPT) {     // final pass: positions from D + gamma S, velocities from alpha D + f2 gamma S
+        g.lpt2       = 5;
+        g.lpt2_sk    = phik;
+        g.lpt2_gamma = -zd::lpt2_ratio(p);
+        g.lpt2_alpha = zd::lpt2_alpha(p);
+        g.lpt2_f2g   = zd::lpt2_f2(p) * g.lpt2_gamma;
+    }
     if (role == zd::ROLE_PHI) g.qPLT = 0;  // the phi pass stops before the displacement algebra (zeldovich.cpp:385-391)
     plan_zstage_jobs(pl);
     if (plan_device_tables(pl, pk, eig, eig_ppd) || plan_block_layout(pl, v1) || plan_stores(pl, rt.twr) || plan_slabs(pl, v1, eig_ppd)) {
@@ -1293,7 +1393,11 @@ static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk,
 static int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
                           int phi_mode, const cplx *phik, zd_plan **out) {
     const zd_params pc = zd::canonical(p_in);
-    const int role = phi_mode == 1 ? zd::ROLE_PHI : phik ? zd::ROLE_PHIK : zd::ROLE_MAIN;
+    const int role = phi_mode == 1 ? zd::ROLE_PHI : phi_mode == 2 ? zd::ROLE_LPT2_GRAD : (phik && !pc.q2LPT) ? zd::ROLE_PHIK : zd::ROLE_MAIN;
+    if (pc.q2LPT && role == zd::ROLE_MAIN && !phik) {  // (zd_plan_create and zd_generate run the second-order round first)
+        fprintf(stderr, "zeldovich_hip: a ZD_q2LPT plan needs the second-order source\n");
+        return 1;
+    }
     const bool have_eig = eig != nullptr && eig_ppd > 0;
     zd_params pa, pb;
     Route ra, rb;
@@ -1788,6 +1892,7 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
                 void *user, zd_stats *out) {
     // ZD_NumGPU: one host thread per GPU, exchange inside the library (zd_multi.cpp).  (ZD_qoneslab finishes ONE plane of one
     // pass and reports the reductions of that slab alone, output.cpp:197: that is this single-GPU path's job.)
+    if (p_in->q2LPT && lpt2_route_check(p_in, p_in->ngpu > 1 ? p_in->ngpu : 1, 0)) return 1;
     if (p_in->ngpu > 1 && p_in->qoneslab < 0) {
         int ndev = 0;
         HIPCHECK(hipGetDeviceCount(&ndev));
@@ -1825,6 +1930,8 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
             p.stream_factor = R2;
         }
     }
+    // ---- ZD_q2LPT: the second-order round (zd_kernels_lpt2.hip); the chooser has counted S(k) beside the passes' stores ----
+    if (p.q2LPT && make_lpt2_source(&p, pk, &d_phik)) return 1;
     zd_plan *pl = nullptr;
     if (plan_create_ex(&p, pk, eig, eig_ppd, 0, 1, 0, d_phik, &pl)) {
         hipFree(d_phik);

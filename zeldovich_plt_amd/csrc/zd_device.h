@@ -63,6 +63,13 @@ struct GenConst {
     // ZD_Version = 1 (zd_kernels_v1.hip): the accepted (phase1, phase2) pairs of cgauss<1> for the rows of the slab being
     // generated, [row of the slab][z][x]; NULL for the version-2 counter streams
     const double2 *v1dev;
+    // second-order displacements (zd_kernels_lpt2.hip).  lpt2 = 1 .. 4: the gradient pass of that number of the second-order round
+    // (the plan's one array holds two Hermitian gradient fields as A + iB); 5: the final pass, which reads the source
+    // lpt2_sk[ky][kz][x] (half-space rows, the layout of phik) beside its own draws: positions from D + lpt2_gamma S,
+    // velocities from lpt2_alpha D + lpt2_f2g S (lpt2_f2g = f2 gamma); 0 everywhere else
+    int lpt2;
+    const zdfft::cplx *lpt2_sk;
+    double lpt2_gamma, lpt2_alpha, lpt2_f2g;
 };
 
 // ZD_Version = 1: one mt19937 stream per yres (src/power_spectrum.cpp:18-25) between two launches of k_v1_draw: the state
@@ -211,7 +218,10 @@ enum JobKind {
     JOB_Z       = 12, // kz (fundamental / k^2) D       q_z = i x its transform
     // PLT field store (PACK_PLTFIELD): the six coefficient sums of the displacement / velocity components
     JOB_PX = 13, JOB_PY = 14, JOB_PZ = 15,      // s_x D, s_y D, s_z D          (q_j = i x its transform)
-    JOB_PFX = 16, JOB_PFY = 17, JOB_PFZ = 18    // f s_x D, f s_y D, f s_z D    (v_j = i x its transform)
+    JOB_PFX = 16, JOB_PFY = 17, JOB_PFZ = 18,   // f s_x D, f s_y D, f s_z D    (v_j = i x its transform)
+    // second-order round (zd_kernels_lpt2.hip): two Hermitian gradient fields with the even real coefficients cA, cB as ONE array
+    JOB_G2_SELF = 19,  // (cA + i cB) D              -> array 0, row ky
+    JOB_G2_TWIN = 20   // conj FFT[(cA - i cB) D]    -> array 0, row N-ky, column N-kx
 };
 // What the store holds.  The reference always transforms the density (Re of its array 0) although only
 // ZD_qdensity writes it out and only its sum of squares is reported; without ZD_qdensity the density is not

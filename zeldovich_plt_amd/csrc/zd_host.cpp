@@ -628,6 +628,10 @@ int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     I("ZD_ExchangePlanes", p->exchange_planes);
     S("ZD_Pk_measured_filename", s->Pk_measured_filename, sizeof(s->Pk_measured_filename));  // band-power table after the run (empty: none)
     I("ZD_PassGroups", p->pass_groups);  // independent groups of GPUs, residue passes dealt round-robin (0: automatic)
+    // second-order displacements (not in the reference; csrc/zd_kernels_lpt2.hip): 0 for a coefficient = the ZD_f_cluster background's
+    I("ZD_q2LPT", p->q2LPT);
+    D("ZD_2LPT_D2", p->lpt2_ratio);
+    D("ZD_2LPT_f2", p->lpt2_f2);
     (void) have_cpd;
     p->cpd = cpd;
 

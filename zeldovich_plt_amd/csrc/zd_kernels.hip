@@ -2537,6 +2537,7 @@ static int genf_kind(const JobList &jobs, bool plt) {
 int launch_gen(const GenConst &g, const GenJumps &J, const JobList &jobs, const StoreLayout &S, int ky0, int nky, int L,
                int residue, int residue2, const void *twN, void *Y, unsigned *tile_ctr, int max_wgs, hipStream_t st) {
     if (gen_zr(L) == 0) return 2;
+    if (g.lpt2) return launch_gen_lpt2(g, J, jobs, S, ky0, nky, L, residue, twN, Y, st);  // second-order plans: zd_kernels_lpt2.hip
 #ifdef ZD_TUNING
     static const bool force_general = getenv("ZD_GEN_GENERAL") != nullptr;
 #else
@@ -2643,6 +2644,7 @@ int launch_zfft(int L, const JobList &jobs, const StoreLayout &S, int ky0, int k
 #define ZCASE(l, e, w) \
     case l: return launch_zfft_t<l, e, w>(jobs, S, ky0, kyloc0, nky, Zq, Y, twL, out, st);
     switch (L) {
+        ZCASE(16, 16, 32)  // one thread per line, no exchange: the second-order final pass at PPD / R = 16 (zd_route.h lpt2_min_zlen)
         ZCASE(32, 16, 32)
         ZCASE(64, 16, 32)
         ZCASE(128, 16, 32)
@@ -2658,7 +2660,7 @@ int launch_zfft(int L, const JobList &jobs, const StoreLayout &S, int ky0, int k
 }
 int zfft_tile_width(int L) {
     switch (L) {
-        case 32: case 64: case 128: return 32;
+        case 16: case 32: case 64: case 128: return 32;
         case 256: case 512: return 16;
         case 1024: case 2048: return 8;
         case 4096: return 4;

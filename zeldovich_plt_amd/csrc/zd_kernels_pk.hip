@@ -19,7 +19,8 @@
 //              sum_vel    sum_j |v_j(k)|^2      ZA: v = vnorm q (src/output.cpp:78-82); PLT: v_j = f q_j, its own field
 //   Refusals.  Configurations whose Nyquist-plane modes stay alive (the nyquist_dead condition of pack_mode, zd_route.h: there the
 //          delivered fields are not transforms of real fields and "power per wavevector" has no single meaning), and
-//          ZD_Version = 1, whose draws are sequential.
+//          ZD_Version = 1, whose draws are sequential; ZD_q2LPT jobs, whose delivered fields hold a second-order part the sweep
+//          does not regenerate.
 //
 // A rank sweeps the half-space rows it owns, ky = rank (mod nranks), ky < N/2, every (kx, kz); a row ky >= 1 stands for itself and
 // its Hermitian twin (weight 2), the plane ky = 0 is visited position by position with the conjugate "loser" rule of k_gen.  The
@@ -353,6 +354,10 @@ extern "C" int zd_plan_measure_power(zd_plan *pl, int32_t bin_width, int64_t nbi
                         "regenerated from a counter\n");
         return 1;
     }
+    if (p.q2LPT) {
+        fprintf(stderr, "zeldovich_hip: band power is not measured on a ZD_q2LPT plan: the sweep regenerates the first-order modes only\n");
+        return 1;
+    }
     const GenConst &g = pl->g;
     if (!(g.kmax == pl->half || (!p.corner_modes && p.k_cutoff >= 1.0))) {
         fprintf(stderr, "zeldovich_hip: band power is not measured while modes on the Nyquist planes stay alive (ZD_CornerModes with "
@@ -409,6 +414,10 @@ extern "C" int zd_measure_power(const zd_params *p_in, const zd_pk *pk, const do
                                 int64_t *count, double *sum_k, double *sum_dens, double *sum_input, double *sum_disp, double *sum_vel) {
     zd_params p = *p_in;
     p.ngpu = 0;
+    if (p.q2LPT) {  // (before a plan — and with it the second-order round — is made)
+        fprintf(stderr, "zeldovich_hip: band power is not measured on a ZD_q2LPT job: the sweep regenerates the first-order modes only\n");
+        return 1;
+    }
     if (p.stream_factor <= 0) {  // any factor whose plan the library accepts: the sweep does not use the store
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {

@@ -128,6 +128,13 @@ int launch_refq_ycols(int n, const void *tw, const AnyChunks &C, void *data, int
 int launch_refq_xphi(int n, const void *tw, void *data, long long pitch, long long nlines, double f_NL, hipStream_t st);
 int launch_refq_emit(const AnyChunks &C, const EpiConst &ec, const void *store, int plane0, int nplanes, int z_first, int z_step, void *records,
                      float *density, Reduce *red, hipStream_t st);
+// ---- second-order displacements (zd_kernels_lpt2.hip) ----
+// the generator of a plan with GenConst::lpt2 != 0 (launch_gen hands such plans over): gradient pairs or the final pass
+int launch_gen_lpt2(const GenConst &g, const GenJumps &J, const JobList &jobs, const StoreLayout &S, int ky0, int nky, int L, int residue,
+                    const void *twN, void *Y, hipStream_t st);
+// x lines of the planes [0, nplanes) of a one-array store in gradient pass `pass` (1 .. 4): inverse transform, the pass's term of
+// the source into acc[z][y][x] (N^3 doubles); pass 4 goes on to acc / N^3 and the forward x transform, in place
+int launch_lpt2_xsrc(const StoreLayout &S, int pass, const void *tw, void *data, double *acc, int nplanes, hipStream_t st);
 // ---- ZD_Version = 1 streams (zd_kernels_v1.hip) ----
 int launch_v1_seed(unsigned long long seed, int block, V1Stream *streams, hipStream_t st);
 int launch_v1_draw(const GenConst &g, int block, int ky0, int ky_stride, int nrows, V1Stream *streams, void *dev, int *err,
@@ -138,3 +145,4 @@ int launch_copy16(const void *in, void *out, long long n16, hipStream_t st);
 
 extern "C" int zdk_upload_bit_table(const zdpcg::BitTable *host);
 extern "C" int zdk_upload_bit_table_fz(const zdpcg::BitTable *host);
+extern "C" int zdk_upload_bit_table_lpt2(const zdpcg::BitTable *host);

@@ -2,6 +2,7 @@
 // shape of the store that plan creation (zd_capi.cpp plan_create_one) builds and that the choosers (zd_choose_stream_factor,
 // zd_choose_pass_groups) size.  Host only: no HIP call, no allocation; the environment only through tune_env (-DZD_TUNING).
 #pragma once
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -33,8 +34,9 @@ inline bool is_pow2(int64_t n) { return n > 0 && (n & (n - 1)) == 0; }
 //   FAM_CONVOLUTION    any other even PPD — or a composite one with options the composite kernels lack: the reference's arrays, one
 //                      rank, the lines as convolutions on the power-of-two engine (zd_kernels_any.hip); R any divisor of PPD
 enum { FAM_POW2 = 0, FAM_COMPOSITE = 1, FAM_REF_COMPOSITE = 2, FAM_CONVOLUTION = 3 };
-// what a plan is for: the main pass, the first f_NL pass (one array holding phi = D/M), the second (D = PhiK * M)
-enum { ROLE_MAIN = 0, ROLE_PHI = 1, ROLE_PHIK = 2 };
+// what a plan is for: the main pass, the first f_NL pass (one array holding phi = D/M), the second (D = PhiK * M), the gradient
+// passes of the second-order round (one array holding two gradient fields of the ZA displacement; zd_kernels_lpt2.hip)
+enum { ROLE_MAIN = 0, ROLE_PHI = 1, ROLE_PHIK = 2, ROLE_LPT2_GRAD = 3 };
 
 struct Route {
     int family = FAM_POW2, pack = PACK_NONE, narray = 0, pstep = 1, npass = 1, R = 1, L = 0, Hq = 0, Zq = 0;
@@ -84,12 +86,37 @@ inline bool plt_dens_split(const zd_params *p, int nranks) {
     return p->qPLT && p->qdensity == 1 && nranks == 1 && composite_options(p) && !tune_env("ZD_NO_DENS_SPLIT");
 }
 
-// reference arrays of a job: density only one (zeldovich.cpp:871-876), PLT four, else two
-inline int ref_arrays(const zd_params *p) { return p->qdensity == 2 ? 1 : (p->qPLT ? 4 : 2); }
+// Second-order displacements (zd_params.q2LPT; definition in zd_kernels_lpt2.hip).  The second-order round keeps the whole field
+// resident on one GPU, on the power-of-two engine, with the counter streams of ZD_Version 2; the final pass fills the reference's
+// four arrays (the PLT shape: velocities are a field of their own), which carry no eigenmodes, no f_NL and no density output here.
+// Live Nyquist planes (ZD_CornerModes with ZD_k_cutoff != 1) are not Hermitian: the source would not be real.  NULL: accepted.
+inline const char *lpt2_refusal(const zd_params *p, int nranks) {
+    if (!p->q2LPT) return nullptr;
+    if (p->q2LPT != 1) return "ZD_q2LPT must be 0 or 1";
+    if (p->qPLT) return "ZD_q2LPT = 1 is not supported together with ZD_qPLT";
+    if (p->f_NL != 0.) return "ZD_q2LPT = 1 is not supported together with ZD_f_NL != 0";
+    if (p->qdensity != 0) return "ZD_q2LPT = 1 is not supported together with a density output (ZD_qdensity)";
+    if (p->version == 1) return "ZD_q2LPT = 1 needs the counter streams of ZD_Version = 2";
+    if (nranks != 1 || p->ngpu > 1) return "ZD_q2LPT = 1 runs on one GPU (one rank)";
+    if (!is_pow2(p->ppd) || p->ppd < 32 || p->ppd > 2048) return "ZD_q2LPT = 1 needs PPD a power of two in [32, 2048]";
+    {   // the nyquist_dead condition of pack_mode
+        const int half = (int) (p->ppd / 2), kmax = (int) ((double) half * (1.0 / p->k_cutoff) + .5);
+        if (!(kmax == half || (!p->corner_modes && p->k_cutoff >= 1.0)))
+            return "ZD_q2LPT = 1 is not supported with live Nyquist planes (ZD_CornerModes with ZD_k_cutoff != 1)";
+    }
+    return nullptr;
+}
+// its coefficients: alpha = vnorm of the f_cluster background (src/output.cpp:78-82); D2 / D1^2 and f2 as given, 0 = that background's
+inline double lpt2_alpha(const zd_params *p) { return (sqrt(1. + 24 * p->f_cluster) - 1) * .25; }
+inline double lpt2_ratio(const zd_params *p) { return p->lpt2_ratio != 0. ? p->lpt2_ratio : -(2 * lpt2_alpha(p) + 1) / (6 * lpt2_alpha(p) + 1); }
+inline double lpt2_f2(const zd_params *p) { return p->lpt2_f2 != 0. ? p->lpt2_f2 : 2 * lpt2_alpha(p); }
+
+// reference arrays of a job: density only one (zeldovich.cpp:871-876), PLT — and the second order's own velocity field — four, else two
+inline int ref_arrays(const zd_params *p) { return p->qdensity == 2 ? 1 : ((p->qPLT || p->q2LPT) ? 4 : 2); }
 
 // Packed stores (zd_device.h PACK_*) the options ask for: without ZD_qdensity the density field is not transformed.
 inline int pack_mode(const zd_params *p, int R) {
-    if (p->store_mode == ZD_STORE_REFERENCE) return PACK_NONE;
+    if (p->store_mode == ZD_STORE_REFERENCE || p->q2LPT) return PACK_NONE;  // (second order: the final pass fills the reference's arrays)
     if ((p->qdensity != 0 && !dens_fields(p)) || p->f_NL != 0.) return PACK_NONE;
     if (p->qoneslab >= 0) return PACK_NONE;  // density_variance is then the sum over that one slab (output.cpp:197)
     {   // The packed stores treat every field as the transform of a REAL field (Hermitian modes) and take
@@ -145,6 +172,10 @@ inline bool fnl_np2_factor_ok(const zd_params *p, int R) {
 // take the even factors (or 1), the reference's arrays any divisor of PPD (their z-residue fold is a plain decimation)
 inline int next_factor(int family, int R) { return family == FAM_POW2 ? 2 * R : family == FAM_COMPOSITE ? (R == 1 ? 2 : R + 2) : R + 1; }
 inline int min_zlen(int family) { return family == FAM_POW2 ? 32 : family == FAM_COMPOSITE ? 12 : 3; }
+// ... and the shortest a GIVEN stream factor may leave a job on the powers of two: the second-order final pass (its own generator and
+// k_zfft on the reference's arrays, zd_kernels_lpt2.hip) also runs z lines of 16 points — one thread per line —, e.g. PPD = 64 at
+// stream factor 4; every other job keeps 32 (the generators and field-store z transforms of zd_kernels.hip start there)
+inline int given_min_zlen(const zd_params *p, int role) { return p->q2LPT && role == ROLE_MAIN ? 16 : min_zlen(FAM_POW2); }
 
 // R <= 0: no factor given — plan creation's default (the first one whose z lines the composite kernels have, else 1).  rank and
 // have_eig take part in plan creation's refusals only.
@@ -154,6 +185,7 @@ inline Route route(const zd_params *p, int R_given, int nranks, int role, int ra
     const int G = nranks < 1 ? 1 : nranks;
     const bool pow2 = is_pow2(N), main = role == ROLE_MAIN;
     int R = R_given > 0 ? R_given : 1;
+    if (const char *why = lpt2_refusal(p, nranks)) r.refuse(true, "%s", why);
     bool comp = false;
     if (!pow2) {
         int Rg = R_given > 0 ? R_given : 2;
@@ -181,7 +213,7 @@ inline Route route(const zd_params *p, int R_given, int nranks, int role, int ra
         if (N % 2 || N < 8 || N > 8192 || nranks != 1 || R < 1 || N % R || N / R < min_zlen(FAM_CONVOLUTION))
             r.refuse(true, "PPD = %lld (neither 2^a nor a supported 2^a 3^b configuration) runs as convolutions on the power-of-two engine: "
                            "even PPD in [8, 8192], one rank, ZD_StreamFactor any divisor of PPD (got %d)", (long long) N, R);
-    } else if (comp ? !np2_stream_factor_ok(N, R) : (!is_pow2(R) || N % R || N / R < min_zlen(FAM_POW2) || N / R > 4096)) {
+    } else if (comp ? !np2_stream_factor_ok(N, R) : (!is_pow2(R) || N % R || N / R < given_min_zlen(p, role) || N / R > 4096)) {
         r.refuse(true, "stream factor %d invalid for PPD %lld", R, (long long) N);  // (z-FFT kernels exist up to length 4096)
     }
     const bool no_split = nranks < 1 || !is_pow2(nranks) || (N / 2) % G || (N / R) % G;
@@ -193,7 +225,7 @@ inline Route route(const zd_params *p, int R_given, int nranks, int role, int ra
     if (p->version == 1 && role != ROLE_PHIK && (p->numblock <= 0 || N % p->numblock || (N / p->numblock) % G))
         r.refuse(false, "ZD_Version = 1 needs ZD_NumBlock dividing PPD and PPD/NumBlock streams divisible by the number of ranks (%d)", nranks);
     // (density only rides on the six-field ZA store of the composite kernels; everywhere else it is one array)
-    r.narray = role == ROLE_PHI ? 1 : (p->qdensity == 2 && !any && dens_fields(p)) ? 2 : ref_arrays(p);
+    r.narray = (role == ROLE_PHI || role == ROLE_LPT2_GRAD) ? 1 : (p->qdensity == 2 && !any && dens_fields(p)) ? 2 : ref_arrays(p);
     if (main && r.narray >= 2 && !any) r.pack = pack_mode(p, R);
     // the field stores need row blocks of FIELD_RB rows per rank and a z FFT <= 2048; PPD > 4096 has no other store worth using
     if (pack_is_fields(r.pack) && (((N / 2) / G) % FIELD_RB || N / R > 2048))

@@ -13,6 +13,9 @@ extern "C" {
  * pack, narray, pstep, npass, R, L, Hq, Zq, dens, dens_only, composite twiddles; `why` (cap bytes) gets the refusal text, "" if the
  * route is accepted.  Returns 0 if accepted, 1 if refused */
 int zd_test_route(const zd_params *p, int32_t R, int32_t nranks, int32_t *out, char *why, int64_t cap);
+/* the coefficients a ZD_q2LPT job runs with (zd_route.h): out[0 .. 2] = alpha (= vnorm), lpt2_ratio and lpt2_f2 with their defaults
+ * resolved */
+void zd_test_lpt2_coefficients(const zd_params *p, double *out);
 /* ---- device test hooks (each needs a GPU) -------------------- */
 /* n counter-addressed draws: out[2*i], out[2*i+1] = the two uint64 of mode (kx,ky,kz)[i] */
 int zd_test_draws(int64_t seed, int64_t n, const int32_t *kxyz, uint64_t *out);
