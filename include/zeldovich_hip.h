@@ -77,8 +77,14 @@ typedef struct zd_params {
      * displacement of the ZA field, scaled by lpt2_ratio = D2 / D1^2.  The two coefficients (ZD_2LPT_D2, ZD_2LPT_f2): 0 = the
      * values of the ZD_f_cluster background, -(2 vnorm + 1) / (6 vnorm + 1) (-3/7 at f_cluster = 1) and 2 vnorm.
      * ZD_Version 2, one GPU, PPD a power of two in [32, 2048]; not with ZD_qPLT, ZD_f_NL, ZD_qdensity, or ZD_CornerModes
-     * together with ZD_k_cutoff != 1 */
+     * together with ZD_k_cutoff != 1.
+     * lpt2_dealias = 1 (ZD_2LPT_dealias, needs q2LPT = 1): the source of the second order is formed on the lattice of 3 PPD / 2 points
+     * per side (Orszag's 3/2 rule, step 2' of the definition), so that no product mode folds back into the band that is kept; one
+     * GPU holds ~81 PPD^3 bytes for that round (PPD <= 1024 on 288 GB); not with ZD_CornerModes.  The field sits in what was the
+     * alignment gap between q2LPT and lpt2_ratio: no other member moves and the size of the struct is unchanged, so a caller built
+     * against the earlier header that zero-fills the struct (as every reader here does) runs as before */
     int32_t q2LPT;
+    int32_t lpt2_dealias;
     double lpt2_ratio, lpt2_f2;
 } zd_params;
 

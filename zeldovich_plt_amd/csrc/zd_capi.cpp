@@ -395,7 +395,11 @@ static int64_t fnl_phi_bytes(const zd_params *p) {
 // ZD_q2LPT memory: the source S(k) (half-space rows, PhiK's layout) stays beside every pass's store; the second-order round before it
 // peaks at its one-array store (every plane, self and twin slots) + the real N^3 accumulator, which S(k) then replaces
 static int64_t lpt2_sk_bytes(int64_t N) { return (N / 2) * N * N * 16; }
-static int64_t lpt2_round_bytes(int64_t N) { return N * N * (N + store_row_pad(N)) * 16 + N * N * N * 8; }
+// ZD_2LPT_dealias: the same round on the lattice of M = 3 N / 2 points per side, (16 + 8) M^3 = 81 N^3 bytes (+ the row pad)
+static int64_t lpt2_round_bytes(const zd_params *p) {
+    const int64_t M = p->lpt2_dealias ? zd::lpt2_dealias_lattice(p->ppd) : p->ppd;
+    return M * M * (M + store_row_pad(M)) * 16 + M * M * M * 8;
+}
 
 // The two halves of a PLT + density run (zd_route.h plt_dens_split) at the PLT half's stream factor R (<= 0: plan creation's
 // default), and whether their shapes fit together: the PLT half on its field store, the density half density-only with the same
@@ -419,7 +423,7 @@ static int choose_stream_factor_one(const zd_params *p, int nranks, int64_t budg
     const int own = is_pow2(N) ? zd::FAM_POW2 : zd::FAM_COMPOSITE;
     // ZA without density: two residues share a pass, so R = 2 is preferred over R = 1 whenever the z FFT is long enough
     const Route r2 = route(p, 2, nranks, zd::ROLE_MAIN);
-    if (p->q2LPT && lpt2_round_bytes(N) > budget_bytes) return -1;
+    if (p->q2LPT && lpt2_round_bytes(p) > budget_bytes) return -1;
     const int64_t lpt2_resident = p->q2LPT ? lpt2_sk_bytes(N) : 0;
     for (int R = r2.legal && r2.pstep == 2 ? 2 : 1; N / R >= zd::min_zlen(own); R = zd::next_factor(own, R)) {
         const Route rt = route(p, R, nranks, zd::ROLE_MAIN);
@@ -483,7 +487,9 @@ int zd_choose_pass_groups(const zd_params *p_in, int ngpu, int64_t budget_bytes,
     const zd_params pc = zd::canonical(p_in), *p = &pc;
     const int64_t N = p->ppd;
     if (ngpu < 1) ngpu = 1;
-    if (const char *why = zd::lpt2_refusal(p, ngpu)) {  // (pass groups included: every GPU would run the second-order round)
+    const char *why = zd::lpt2_refusal(p, ngpu);  // (pass groups included: every GPU would run the second-order round)
+    if (!why) why = zd::lpt2_dealias_refusal(p);
+    if (why) {
         fprintf(stderr, "zeldovich_hip: %s\n", why);
         return 1;
     }
@@ -682,7 +688,16 @@ static int make_phik(const zd_params *p, const zd_pk *pk, cplx **d_phik) {
 // rows, already scaled by N^-3 (owned by the caller).  Four gradient passes over one one-array store — generator, z and y stages of
 // the plan, then the x lines into the real accumulator — and the forward transforms of the f_NL phi round.  The accumulator is freed
 // before S(k) is allocated: the peak is lpt2_round_bytes.
+static int make_lpt2_source_dealiased(const zd_params *p, const zd_pk *pk, cplx **d_sk);
+// the round's peak against the free memory, asked before anything is built (the figure is the message)
+static int lpt2_round_fits(const zd_params *p, int64_t free_bytes) {
+    if (lpt2_round_bytes(p) <= free_bytes) return 1;
+    fprintf(stderr, "zeldovich_hip: ZD_q2LPT%s needs %.1f GB of HBM for the second-order round at PPD %lld, %.1f GB are free\n",
+            p->lpt2_dealias ? " with ZD_2LPT_dealias = 1" : "", lpt2_round_bytes(p) / 1e9, (long long) p->ppd, free_bytes / 1e9);
+    return 0;
+}
 static int make_lpt2_source(const zd_params *p, const zd_pk *pk, cplx **d_sk) {
+    if (p->lpt2_dealias) return make_lpt2_source_dealiased(p, pk, d_sk);
     const int64_t N  = p->ppd;
     zd_params pp     = *p;
     pp.stream_factor = 1;   // the forward z transform needs every plane of a row
@@ -696,7 +711,7 @@ static int make_lpt2_source(const zd_params *p, const zd_pk *pk, cplx **d_sk) {
         if (zd_store_alloc(&d_grad, (size_t) zd_plan_exchange_bytes(ph)) != hipSuccess
             || zd_store_alloc(&d_acc, (size_t) N * N * N * sizeof(double)) != hipSuccess) {
             fprintf(stderr, "zeldovich_hip: ZD_q2LPT needs %.1f GB of HBM for the second-order round at PPD %lld\n",
-                    lpt2_round_bytes(N) / 1e9, (long long) N);
+                    lpt2_round_bytes(p) / 1e9, (long long) N);
             break;
         }
         int pass = 1;
@@ -718,6 +733,77 @@ static int make_lpt2_source(const zd_params *p, const zd_pk *pk, cplx **d_sk) {
         while ((1 << lN) < (int) N) lN++;
         if (zd::launch_fnl_stage(1, ph->S, 0.0, ph->d_twN, d_grad, nullptr, (int) N, lN, 0)) break;
         if (zd::launch_fnl_stage(2, ph->S, 0.0, ph->d_twN, d_grad, *d_sk, (int) N, lN, 0)) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        frc = 0;
+    } while (0);
+    hipFree(d_acc);
+    hipFree(d_grad);
+    zd_plan_destroy(ph);
+    if (frc) {
+        hipFree(*d_sk);
+        *d_sk = nullptr;
+    }
+    return frc;
+}
+// ZD_2LPT_dealias = 1 (step 2' of the definition): the same round on the lattice of M = 3 N / 2 points per side.  The plan of the gradient
+// passes is a plan AT M — ZD_k_cutoff x 1.5, the same box, the same seed: the counter-addressed draws and the zero rule give exactly the
+// modes of the N run, at their signed wavenumbers — on a one-array store [z][y][x] of the reference-array family, every line through
+// the composite transforms (Q = 3).  k_xlpt2q (zd_kernels_lpt2q.hip) forms S on the M^3 accumulator and, on pass 4, takes S / M^3 through
+// the x transform; the y columns |kx| < N/2 follow in place, and the z lines of the columns |kx| < N/2, 0 <= ky < N/2 go, truncated
+// to |kz| < N/2 and conjugated (three inverse transforms of a real field are the conjugate of its forward transform), straight
+// into S(k)[ky][kz][x] of the N layout.
+static int make_lpt2_source_dealiased(const zd_params *p, const zd_pk *pk, cplx **d_sk) {
+    const int64_t N = p->ppd, M = zd::lpt2_dealias_lattice(N);
+    *d_sk           = nullptr;
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || !lpt2_round_fits(p, (int64_t) free_b)) return 1;
+    }
+    zd_params pp     = *p;
+    pp.ppd           = M;
+    pp.k_cutoff      = p->k_cutoff * 1.5;
+    pp.nyquist       = p->nyquist * 1.5;  // (k2_cutoff = nyquist^2 / k_cutoff^2 may move by an ulp: it decides differently only for an integer
+                                          // |k|^2 ON the cut, and at k_cutoff = 1, 2 that is |k|^2 = kmax^2 = 4^a, the modes (kmax, 0, 0) the
+                                          // |k_i| == kmax rule kills anyway; kmax itself is checked below)
+    pp.lpt2_dealias  = 0;
+    pp.stream_factor = 1;
+    pp.qoneslab      = -1;
+    zd_plan *ph      = nullptr;
+    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 2, nullptr, &ph)) return 1;
+    void *d_grad = nullptr, *d_acc = nullptr;
+    int frc      = 1;
+    do {
+        if (!ph->d_twr_n || ph->N != M || ph->g.kmax != (int) ((double) (N / 2) * (1.0 / p->k_cutoff) + .5)) {
+            fprintf(stderr, "zeldovich_hip: ZD_2LPT_dealias: the plan on the %lld lattice does not carry the modes of PPD %lld\n", (long long) M,
+                    (long long) N);
+            break;
+        }
+        if (zd_store_alloc(&d_grad, (size_t) zd_plan_exchange_bytes(ph)) != hipSuccess
+            || zd_store_alloc(&d_acc, (size_t) M * M * M * sizeof(double)) != hipSuccess) {
+            fprintf(stderr, "zeldovich_hip: ZD_q2LPT with ZD_2LPT_dealias = 1 needs %.1f GB of HBM for the second-order round at PPD %lld\n",
+                    lpt2_round_bytes(p) / 1e9, (long long) N);
+            break;
+        }
+        const long long pitch = ph->AL.pitch, plane = M * pitch;
+        int pass = 1;
+        for (; pass <= 4; pass++) {
+            ph->g.lpt2 = pass;
+            if (zd_plan_stage_z(ph, 0, d_grad, 0) || zd_plan_stage_y(ph, d_grad, 0)) break;
+            if (zd::launch_lpt2q_xsrc((int) M, ph->d_twr_n, pass, d_grad, pitch, M * M, (double *) d_acc, 0)) break;
+        }
+        if (pass <= 4) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        hipFree(d_acc);
+        d_acc = nullptr;
+        if (zd_store_alloc((void **) d_sk, (size_t) lpt2_sk_bytes(N)) != hipSuccess) {
+            fprintf(stderr, "zeldovich_hip: ZD_q2LPT needs %.1f GB of HBM for the second-order source at PPD %lld\n",
+                    lpt2_sk_bytes(N) / 1e9, (long long) N);
+            break;
+        }
+        // y columns of the planes, only those that are kept: x = kx in [0, N/2) and x = M + kx, kx in (-N/2, 0)
+        if (zd::launch_refq_cols((int) M, ph->d_twr_n, d_grad, plane, pitch, (int) (N / 2), (int) M, -1, 0)) break;
+        if (zd::launch_refq_cols((int) M, ph->d_twr_n, (cplx *) d_grad + (M - N / 2 + 1), plane, pitch, (int) (N / 2 - 1), (int) M, -1, 0)) break;
+        if (zd::launch_lpt2q_zsrc((int) M, (int) N, ph->d_twr_n, d_grad, pitch, *d_sk, 0)) break;
         if (hipDeviceSynchronize() != hipSuccess) break;
         frc = 0;
     } while (0);
@@ -1892,7 +1978,7 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
                 void *user, zd_stats *out) {
     // ZD_NumGPU: one host thread per GPU, exchange inside the library (zd_multi.cpp).  (ZD_qoneslab finishes ONE plane of one
     // pass and reports the reductions of that slab alone, output.cpp:197: that is this single-GPU path's job.)
-    if (p_in->q2LPT && lpt2_route_check(p_in, p_in->ngpu > 1 ? p_in->ngpu : 1, 0)) return 1;
+    if ((p_in->q2LPT || p_in->lpt2_dealias) && lpt2_route_check(p_in, p_in->ngpu > 1 ? p_in->ngpu : 1, 0)) return 1;
     if (p_in->ngpu > 1 && p_in->qoneslab < 0) {
         int ndev = 0;
         HIPCHECK(hipGetDeviceCount(&ndev));
@@ -1904,6 +1990,7 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
     const int64_t N = p.ppd;
     size_t free_b = 0, total_b = 0;
     HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+    if (p.q2LPT && p.lpt2_dealias && !lpt2_round_fits(&p, (int64_t) free_b - ((int64_t) 16 << 30))) return 1;
     if (p.stream_factor <= 0) {
         // leave 16 GB for tables, the folded-input slabs (~3 GB), the record ring (8 GB) and the runtime
         const int64_t budget = (int64_t) free_b - ((int64_t) 16 << 30);

@@ -632,6 +632,7 @@ int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     I("ZD_q2LPT", p->q2LPT);
     D("ZD_2LPT_D2", p->lpt2_ratio);
     D("ZD_2LPT_f2", p->lpt2_f2);
+    I("ZD_2LPT_dealias", p->lpt2_dealias);  // the source on the 3 PPD / 2 lattice (csrc/zd_kernels_lpt2q.hip)
     (void) have_cpd;
     p->cpd = cpd;
 

@@ -9,6 +9,13 @@
 //      the Nyquist planes are dead as in the first order.  Inverse-transformed to the lattice, unnormalised, like q.
 //   2. Source.  S(x) = sum_{a<b} [ psi1_{a,a} psi1_{b,b} - (psi1_{a,b})^2 ], pointwise on the N^3 lattice.  No de-aliasing
 //      (2LPTic's convention).
+//   2'. De-aliased source (zd_params.lpt2_dealias = 1, ZD_2LPT_dealias; Orszag's 3/2 rule).  Steps 1 - 3 run on the lattice of M = 3 N / 2
+//      points per side.  The six gradient fields carry the same modes as before — the alive modes of the PPD = N run, Nyquist planes
+//      of N dead — at their signed wavenumbers in an M^3 cube, zero elsewhere, inverse-transformed unnormalised to M^3.  S(x) is formed
+//      pointwise on M^3.  S(k) = M^-3 sum_x S(x) e^{-2 pi i k.x / M} is kept only for |k_i| < N/2 and multiplied by the alive mask of
+//      the N run, with S(0) = 0.  Steps 4 and 5 are unchanged and run at N.  A product of two modes with |k_i| < N/2 has |k_i| < N;
+//      on M = 3 N / 2 points it folds only to |k_i| > N/2, which is dropped: the S(k) kept is exact.  (At ZD_k_cutoff >= 1.5 nothing
+//      aliases in step 2 either, and the two agree to rounding.)
 //   3. Forward transform.  S(k) = N^-3 sum_x S(x) e^{-2 pi i k.x / N}, multiplied by the same alive mask as D(k): the zero rule
 //      (Nyquist planes, ZD_k_cutoff, the corner rule), with S(0) = 0.  (The one-mode filter is not part of the mask.)
 //   4. Second-order displacement.  psi2_j(k) = i k_j gamma S(k) / k^2, gamma = -lpt2_ratio: div psi2 = -gamma S.
@@ -28,6 +35,11 @@
 //   On pass 4 the same kernel scales by N^-3 and transforms the row forward in place; k_yfwd and k_zfwd of the f_NL round then give
 //   the half-space S(k)[ky][kz][x].  D is REGENERATED in every pass (counter-addressed draws; modes_cached stays 0): keeping
 //   D would cost 8 N^3 bytes beside the 24 N^3 of the round for a generator that is a small part of a pass.
+//   De-aliased round (make_lpt2_source_dealiased; kernels: zd_kernels_lpt2q.hip): the same four passes with a plan AT the lattice M
+//   (ZD_k_cutoff x 1.5, same box and seed: the counter-addressed draws and the zero rule give exactly the modes of the N run), on a
+//   one-array store [z][y][x] of the reference-array family: k_gen_lpt2<2> -> k_refq_cols (z) -> k_any_scatter -> k_refq_cols (y) ->
+//   k_xlpt2q into a real M^3 accumulator; then the y columns |kx| < N/2 and k_lpt2q_zsrc, which truncates to the N cube and writes
+//   S(k)[ky][kz][x] in the N layout.  Peak (16 + 8) M^3 = 81 N^3 bytes.
 //   Final pass: k_gen_lpt2<7> forms the seven jobs of the reference's four arrays (density + i qx | qy + i qz | i vx | vy + i vz,
 //   the PLT shape) from its own draws and S(k): the density from D, positions from D + gamma S, velocities from
 //   alpha D + f2 gamma S with the ZA coefficients s_j = k_j fundamental / k^2.  The z, y and x stages and the PLT epilogue (velocity

@@ -135,6 +135,12 @@ int launch_gen_lpt2(const GenConst &g, const GenJumps &J, const JobList &jobs, c
 // x lines of the planes [0, nplanes) of a one-array store in gradient pass `pass` (1 .. 4): inverse transform, the pass's term of
 // the source into acc[z][y][x] (N^3 doubles); pass 4 goes on to acc / N^3 and the forward x transform, in place
 int launch_lpt2_xsrc(const StoreLayout &S, int pass, const void *tw, void *data, double *acc, int nplanes, hipStream_t st);
+// ---- the de-aliased second-order round on the lattice of m = 3 n / 2 points per side (zd_kernels_lpt2q.hip); tw as for launch_refq_* ----
+// x lines l < nlines at data[l * pitch] in gradient pass `pass` (1 .. 4): launch_lpt2_xsrc's contract with acc[l * m + x] (m^3 doubles)
+int launch_lpt2q_xsrc(int m, const void *tw, int pass, void *data, long long pitch, long long nlines, double *acc, hipStream_t st);
+// the last z lines of the store [z][y][x] (row pitch `pitch`): columns |kx| < n/2, rows 0 <= ky < n/2, outputs |kz| < n/2, conjugated,
+// into sk[ky][kz][x] of the n layout (zeros on its Nyquist planes)
+int launch_lpt2q_zsrc(int m, int n, const void *tw, const void *store, long long pitch, void *sk, hipStream_t st);
 // ---- ZD_Version = 1 streams (zd_kernels_v1.hip) ----
 int launch_v1_seed(unsigned long long seed, int block, V1Stream *streams, hipStream_t st);
 int launch_v1_draw(const GenConst &g, int block, int ky0, int ky_stride, int nrows, V1Stream *streams, void *dev, int *err,

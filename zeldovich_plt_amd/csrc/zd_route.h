@@ -106,6 +106,19 @@ inline const char *lpt2_refusal(const zd_params *p, int nranks) {
     }
     return nullptr;
 }
+// ZD_2LPT_dealias (zd_params.lpt2_dealias; step 2' of the definition, zd_kernels_lpt2.hip): the second-order round on the lattice of
+// M = 3 PPD / 2 points per side, every line through the composite transforms of zd_kernels_np2_ref.hip (zd_kernels_lpt2q.hip).  The
+// corner rule decided on that lattice would keep modes beyond the PPD cube.  NULL: accepted (asked after lpt2_refusal).
+inline int64_t lpt2_dealias_lattice(int64_t N) { return 3 * N / 2; }
+inline const char *lpt2_dealias_refusal(const zd_params *p) {
+    if (!p->lpt2_dealias) return nullptr;
+    if (p->lpt2_dealias != 1) return "ZD_2LPT_dealias must be 0 or 1";
+    if (p->q2LPT != 1) return "ZD_2LPT_dealias = 1 needs ZD_q2LPT = 1";
+    if (p->corner_modes) return "ZD_2LPT_dealias = 1 is not supported together with ZD_CornerModes";
+    if (p->ppd % 2 || !refq_supported_len((int) lpt2_dealias_lattice(p->ppd)))
+        return "ZD_2LPT_dealias = 1 needs a PPD whose 3 PPD / 2 has a composite line transform";
+    return nullptr;
+}
 // its coefficients: alpha = vnorm of the f_cluster background (src/output.cpp:78-82); D2 / D1^2 and f2 as given, 0 = that background's
 inline double lpt2_alpha(const zd_params *p) { return (sqrt(1. + 24 * p->f_cluster) - 1) * .25; }
 inline double lpt2_ratio(const zd_params *p) { return p->lpt2_ratio != 0. ? p->lpt2_ratio : -(2 * lpt2_alpha(p) + 1) / (6 * lpt2_alpha(p) + 1); }
@@ -185,7 +198,13 @@ inline Route route(const zd_params *p, int R_given, int nranks, int role, int ra
     const int G = nranks < 1 ? 1 : nranks;
     const bool pow2 = is_pow2(N), main = role == ROLE_MAIN;
     int R = R_given > 0 ? R_given : 1;
-    if (const char *why = lpt2_refusal(p, nranks)) r.refuse(true, "%s", why);
+    // (the plan of the second-order round's gradient passes belongs to a job that was asked as ROLE_MAIN before; with ZD_2LPT_dealias it
+    // sits on the 3 PPD / 2 lattice, on the reference's arrays with the composite transforms)
+    const bool grad = role == ROLE_LPT2_GRAD;
+    if (!grad) {
+        if (const char *why = lpt2_refusal(p, nranks)) r.refuse(true, "%s", why);
+        if (const char *why = lpt2_dealias_refusal(p)) r.refuse(true, "%s", why);
+    }
     bool comp = false;
     if (!pow2) {
         int Rg = R_given > 0 ? R_given : 2;
@@ -199,7 +218,7 @@ inline Route route(const zd_params *p, int R_given, int nranks, int role, int ra
                && (N / 2) % (G * FIELD_RB) == 0;
         if (comp) R = Rg;
     }
-    r.twr    = !comp && fnl_np2_factor_ok(p, R);
+    r.twr    = !comp && (fnl_np2_factor_ok(p, R) || (grad && !pow2 && R == 1 && refq_supported_len((int) N)));
     r.family = pow2 ? FAM_POW2 : comp ? FAM_COMPOSITE : r.twr ? FAM_REF_COMPOSITE : FAM_CONVOLUTION;
     const bool any = !pow2 && !comp;
     if (pow2 && (N < 32 || N > 16384)) r.refuse(true, "PPD = %lld unsupported (powers of two: 32 ... 16384)", (long long) N);
