@@ -277,6 +277,13 @@ typedef struct zd_param_strings {
     double f_NL, n_s, Omega_M;
     int64_t np;
     char Pk_measured_filename[1024]; /* ZD_Pk_measured_filename (optional, not in the reference): the CLI writes the band-power table there */
+    /* ZD_SelfCheck = n (optional, not in the reference; 0 < n <= 64, default 0 = off): after the run the CLI compares the records it
+     * delivered at n lattice sites with zd_direct_sum and exits 1 if max |record - direct sum| / max|q| exceeds SelfCheck_tol
+     * (ZD_SelfCheck_tol; default 1e-10 for the float64 formats, 1e-6 for the float32 ones); ZD_SelfCheck_filename: the site list
+     * with both sets of values.  Refused by the reader together with what zd_direct_sum refuses, and with ZD_f_NL */
+    double SelfCheck_tol;
+    int32_t SelfCheck;
+    char SelfCheck_filename[1024];
 } zd_param_strings;
 int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s);
 
@@ -314,6 +321,20 @@ int zd_plan_measure_power(zd_plan *plan, int32_t bin_width, int64_t nbins, int64
                           double *sum_input, double *sum_disp, double *sum_vel, void *hip_stream);
 int zd_measure_power(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t bin_width, int64_t nbins,
                      int64_t *count, double *sum_k, double *sum_dens, double *sum_input, double *sum_disp, double *sum_vel);
+
+/* ---- direct summation at sample sites ----------------------------------------------------------
+ * The same sweep accumulating F(k) e^{2 pi i k.x / ppd} at up to 64 lattice sites instead of binning: a check of the delivered records
+ * that is independent of the stores, the fold, the transform passes, the packing and the epilogue, at any size and option; the
+ * definition is pinned in csrc/zd_kernels_ds.hip.  sites_zyx: HOST array of nsites x (z, y, x), each in [0, ppd); out7: HOST array of
+ * nsites x 7 doubles = qx, qy, qz, vx, vy, vz, density — what an RVdoubleZel run with ZD_qdensity = 1 delivers at those sites (formats
+ * without velocities or runs without density simply ignore those columns).  zd_plan_direct_sum sums the rows of this rank (ky = rank
+ * mod nranks): the results of the ranks add up to the whole; a ZD_f_NL plan uses its own PhiK.  The call returns when the sums are in
+ * out7; two calls on one plan return the same bits.  zd_direct_sum is the one-call form on a one-rank plan.  Refused (message,
+ * non-zero): configurations whose Nyquist-plane modes stay alive (ZD_CornerModes with ZD_k_cutoff != 1), ZD_Version = 1, q2LPT plans,
+ * a site outside the lattice, nsites < 1 or > 64, NULL arrays. */
+int zd_plan_direct_sum(zd_plan *plan, int64_t nsites, const int64_t *sites_zyx, double *out7, void *hip_stream);
+int zd_direct_sum(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int64_t nsites, const int64_t *sites_zyx,
+                  double *out7);
 
 /* ---- diagnostics ------------------------------------------------------------------------------
  * Which kernel variants this process has launched so far, and how often: one line "count<TAB>line<TAB>launcher" per launch

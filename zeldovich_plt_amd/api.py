@@ -68,6 +68,7 @@ class ZdParamStrings(C.Structure):
         ("qPk_fix_to_mean", C.c_int32), ("version", C.c_int32),
         ("f_NL", C.c_double), ("n_s", C.c_double), ("Omega_M", C.c_double), ("np", C.c_int64),
         ("Pk_measured_filename", C.c_char * 1024),
+        ("SelfCheck_tol", C.c_double), ("SelfCheck", C.c_int32), ("SelfCheck_filename", C.c_char * 1024),
     ]
 
 
@@ -83,6 +84,7 @@ EXPORTED_SYMBOLS = [
     "zd_params_from_file", "zd_pk_create_from_file", "zd_pk_create_powerlaw", "zd_pk_power",
     "zd_pk_sigmaR", "zd_pk_destroy", "zd_load_eigmodes", "zd_free", "zd_comm_abort", "zd_comm_traffic", "zd_choose_pass_groups", "zd_plan_run_passes", "zd_comm_probe", "zd_choose_pass_groups_measured",
     "zd_dispatch_report", "zd_power_nbins", "zd_plan_measure_power", "zd_measure_power",
+    "zd_plan_direct_sum", "zd_direct_sum",
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
@@ -184,6 +186,8 @@ def _load(path, testing):
     L.zd_power_nbins.restype = i64
     L.zd_plan_measure_power.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp]
     L.zd_measure_power.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i64, vp, vp, vp, vp, vp, vp]
+    L.zd_plan_direct_sum.argtypes = [vp, i64, vp, vp, vp]
+    L.zd_direct_sum.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i64, vp, vp]
     L.zd_dispatch_report.argtypes = [C.c_char_p, i64]
     L.zd_dispatch_report.restype = i64
     return L
@@ -402,6 +406,39 @@ def measure_power(params, ps, eig=None, bin_width=1):
     return _power_derived(out)
 
 
+MAX_SITES = 64  # sites per direct_sum call
+
+
+def _site_array(sites, ppd):
+    """int64 [nsites, 3] of (z, y, x), checked before anything touches the GPU"""
+    s = np.asarray(sites)
+    if s.size == 0 or s.ndim != 2 or s.shape[1] != 3:
+        raise ValueError("direct_sum: sites must be a non-empty [nsites, 3] array of (z, y, x)")
+    if not np.issubdtype(s.dtype, np.integer):
+        raise ValueError("direct_sum: sites must be integers")
+    if s.shape[0] > MAX_SITES:
+        raise ValueError("direct_sum: at most %d sites per call (got %d)" % (MAX_SITES, s.shape[0]))
+    if s.min() < 0 or s.max() >= int(ppd):
+        raise ValueError("direct_sum: every site must lie in [0, %d)^3" % int(ppd))
+    return np.ascontiguousarray(s, dtype=np.int64)
+
+
+def direct_sum(params, ps, sites, eig=None):
+    """The fields a run with these parameters delivers at the lattice sites [(z, y, x), ...], by direct summation over the modes it
+    realises (zd_direct_sum: one sweep on cuda:0 per 8 sites, no transform and no store; definition in csrc/zd_kernels_ds.hip).
+    Returns float64 [nsites, 7] = qx, qy, qz, vx, vy, vz, density."""
+    s = _site_array(sites, params.ppd)
+    L = load_library()
+    out = np.zeros((s.shape[0], 7), dtype=np.float64)
+    eigp, eig_ppd = (None, 0)
+    if eig is not None:
+        eig = np.ascontiguousarray(eig, dtype=np.float64)
+        eigp, eig_ppd = eig.ctypes.data, eig.shape[0]
+    if L.zd_direct_sum(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, s.shape[0], s.ctypes.data, out.ctypes.data):
+        raise RuntimeError("zd_direct_sum failed; see stderr")
+    return out
+
+
 def generate_planes(params, ps, on_plane, eig=None):
     """zd_generate with a per-plane consumer: on_plane(z, records[y, x]) sees a VIEW valid only during the call (like the
     reference's single output buffer); nothing is accumulated here.  Returns the statistics + the number of planes."""
@@ -495,6 +532,14 @@ class Plan:
         if self.L.zd_plan_measure_power(self.h, int(bin_width), nb, *ptrs, stream):
             raise RuntimeError("zd_plan_measure_power failed; see stderr")
         return _power_derived(out)
+
+    def direct_sum(self, sites, stream=0):
+        """direct summation at the sites over this rank's rows (zd_plan_direct_sum): the arrays of the ranks add up to the whole"""
+        s = _site_array(sites, self.params.ppd)
+        out = np.zeros((s.shape[0], 7), dtype=np.float64)
+        if self.L.zd_plan_direct_sum(self.h, s.shape[0], s.ctypes.data, out.ctypes.data, stream):
+            raise RuntimeError("zd_plan_direct_sum failed; see stderr")
+        return out
 
     def stats(self):
         st = ZdStats()

@@ -633,6 +633,10 @@ int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     D("ZD_2LPT_D2", p->lpt2_ratio);
     D("ZD_2LPT_f2", p->lpt2_f2);
     I("ZD_2LPT_dealias", p->lpt2_dealias);  // the source on the 3 PPD / 2 lattice (csrc/zd_kernels_lpt2q.hip)
+    // the run checks itself: records at n sites against the direct summation over the modes (csrc/zd_kernels_ds.hip)
+    I("ZD_SelfCheck", s->SelfCheck);
+    D("ZD_SelfCheck_tol", s->SelfCheck_tol);
+    S("ZD_SelfCheck_filename", s->SelfCheck_filename, sizeof(s->SelfCheck_filename));
     (void) have_cpd;
     p->cpd = cpd;
 
@@ -716,6 +720,29 @@ int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     else if (p->qdensity != 2) {
         fprintf(stderr, "Error: unknown ICFormat \"%s\". Aborting.\n", s->ICFormat);  // output.cpp:272-277
         return 1;
+    }
+    if (s->SelfCheck) {  // what zd_direct_sum refuses is refused here, before anything is generated
+        const char *why = nullptr;
+        if (s->SelfCheck < 0 || s->SelfCheck > 64)
+            why = "takes 1 to 64 sites";
+        else if (s->SelfCheck_tol < 0)
+            why = "needs ZD_SelfCheck_tol >= 0";
+        else if (s->version == 1)
+            why = "does not run with ZD_Version = 1: its draws are sequential, no mode can be regenerated from a counter";
+        else if (p->q2LPT)
+            why = "does not run with ZD_q2LPT: the direct summation regenerates the first-order modes only";
+        else if (s->f_NL != 0.)
+            why = "does not run with ZD_f_NL: the check would run the phi round a second time, on one GPU";
+        else if (p->corner_modes && (int) ((double) (p->ppd / 2) / p->k_cutoff + .5) != (int) (p->ppd / 2))
+            why = "does not run while modes on the Nyquist planes stay alive (ZD_CornerModes with ZD_k_cutoff != 1)";
+        else if (p->qoneslab >= p->ppd)
+            why = "needs ZD_qoneslab inside the lattice: the sites are chosen on that slab";
+        if (why) {
+            fprintf(stderr, "Invalid Parameters given: ZD_SelfCheck = %d %s\n", (int) s->SelfCheck, why);
+            return 1;
+        }
+        if (s->SelfCheck_tol == 0)  // the project's parity bound for the float64 records, the format tests' bound for the float32 ones
+            s->SelfCheck_tol = p->icformat == ZD_FMT_RVDOUBLEZEL || p->icformat == ZD_FMT_ZEL ? 1e-10 : 1e-6;
     }
     return 0;
 }

@@ -44,11 +44,14 @@
 #include "zd_plan.h"
 #include "zd_launch.h"
 #include "zd_genmath.h"
+#include "zd_sweep.h"
 
 using namespace zd;
 using zdfft::cplx;
 using zdpcg::u128;
 using namespace zdgen;
+using zdsweep::SweepJumps;
+using zdsweep::SweepMode;
 
 namespace {
 
@@ -56,22 +59,6 @@ constexpr int PK_BX  = 256;  // threads (consecutive x) per workgroup
 constexpr int PK_ZC  = 256;  // z indices one thread walks
 constexpr int PK_WIN = 384;  // bins of the LDS window: sqrt(255^2 + 255^2) + 2 = 363 at w = 1
 constexpr int PK_NV  = 5;    // sum_k, sum_dens, sum_input, sum_disp, sum_vel
-constexpr int PK_NBIT = 34;  // the first mode of a thread lies < 2^33 + 1 draws into its row
-
-struct PkJumps {
-    zdpcg::Affine bit[PK_NBIT];  // 2^i draws
-    // z -> z + 1 with the state one draw ahead and two draws consumed (2 * 65536 * rows - 1 draws); index 1: the step crosses the
-    // z = N/2 wrap of the counter (rows N/2 + 1 .. live at 65536 - N + z, zeldovich.cpp:335); _full: no draw consumed
-    zdpcg::Affine next[2], next_full[2];
-};
-
-__device__ __forceinline__ u128 pk_advance(const PkJumps &J, u128 s, uint64_t delta) {
-    for (int i = 0; i < PK_NBIT; i++) {
-        if ((delta >> i) == 0) break;
-        if ((delta >> i) & 1ULL) s = zdpcg::apply(J.bit[i], s);
-    }
-    return s;
-}
 
 // floor(sqrt(k2i)) from an approximate root
 __device__ __forceinline__ int pk_isqrt_fix(int k2i, double root) {
@@ -89,7 +76,7 @@ struct PkRun {
 };
 
 template <bool PLT, bool PLAW, bool FAST>
-__global__ __launch_bounds__(PK_BX) void k_pk_sweep(GenConst g, PkJumps J, int ky_first, int ky_stride, int lG, int zc, int w, int nbins,
+__global__ __launch_bounds__(PK_BX) void k_pk_sweep(GenConst g, SweepJumps J, int ky_first, int ky_stride, int lG, int zc, int w, int nbins,
                                                      double vnorm2, unsigned long long *__restrict__ gcount, double *__restrict__ gsum) {
     extern __shared__ double pk_lds[];
     const int ntab = FAST ? g.genf_n : 0;
@@ -153,143 +140,44 @@ __global__ __launch_bounds__(PK_BX) void k_pk_sweep(GenConst g, PkJumps J, int k
         run.v[4] += vel;
     };
 
-    u128 s = 0;
-    if (ky != 0 && act && !g.phik) {  // state one step ahead of the first mode's counter
-        const int kz0 = z0 > half ? z0 - N : z0;
-        s = pk_advance(J, g.row_state[ky], 2ULL * ((uint64_t) (kz0 & 65535) * 65536ULL + (uint64_t) (kx & 65535)) + 1ULL);
+    // what the sweep takes from a visited mode (the walk: zd_sweep.h)
+    EigXY exy = {};
+    EigAxis eax = {0, 0, 0.0}, eay = {0, 0, 0.0};
+    if constexpr (PLT) {
+        eax = eig_axis(g, eig_index_x(g, kx));
+        eay = eig_axis(g, ky);
+        if constexpr (FAST) exy = eig_xy(g, eax, eay);
     }
-    if constexpr (FAST) {  // rows ky >= 1, the arithmetic of genf_tile
-        const int kxy2  = kx * kx + ky * ky;
-        const bool dead = !act || (kx < 0 ? -kx : kx) == g.kmax || ky == g.kmax;  // zeldovich.cpp:350
-        EigXY exy = {};
-        if constexpr (PLT) exy = eig_xy(g, eig_axis(g, eig_index_x(g, kx)), eig_axis(g, ky));
-#pragma unroll 1
-        for (int z = z0; z < z1; z++) {
-            const int kz  = z > half ? z - N : z;
-            const int k2i = kxy2 + kz * kz;
-            const bool live = !dead && (kz < 0 ? -kz : kz) != g.kmax && (g.corner_modes || k2i < g.k2i_cut);
-            const int sel   = z == half;
-            if (!__any(live)) {  // all 64 modes zeroed: only the walk moves on
-                s = zdpcg::apply(J.next_full[sel], s);
-                continue;
-            }
-            const uint64_t r1 = zdpcg::output(s);
-            const u128 s2     = zdpcg::step(s);
-            const uint64_t r2 = zdpcg::output(s2);
-            s = zdpcg::apply(J.next[sel], s2);
-            // ---- cgauss<2> (power_spectrum.cpp:338-359) as in genf_tile ----
-            const double k2v = (double) k2i * g.fundamental2;
-            const double P   = genf_power<PLAW>(g, T, k2v);
-            const double ik2 = frcp(k2v);
-            const uint64_t m1 = r1 + 1ULL;
-            double v = P;
-            if (!g.fixed_power) v = -P * flog(u64_to_double(m1), 64, T);
-            v = (m1 == 0 && !g.fixed_power) || !live ? 0.0 : v;
-            const double amp = sqrt_pos(v);
-            double sn, cs;
-            sincos_u01(u64_to_double(r2 + 1ULL), T, sn, cs);
-            const double dr = amp * cs, di = amp * sn;
-            const double d2 = fma(dr, dr, di * di);
-            double disp, vel;
-            if constexpr (PLT) {
-                double e[4];
-                eigenmode_fast(g, kx, ky, kz, exy, eig_axis(g, eig_index_z(g, kz)), e);
-                const double f = (sqrt_pos(1. + 24 * e[3] * g.f_cluster) - 1) * .25;
-                double rescale = 1.0;
-                if (g.qPLTrescale) rescale = fexp(g.ln_growth_ratio * (g.target_f - f), T);
-                const double sx = rescale * e[0], sy = rescale * e[1], sz = rescale * e[2];
-                disp = (sx * sx + sy * sy + sz * sz) * d2;
-                vel  = f * f * disp;
-            } else {
-                const double q = g.fundamental * ik2;
-                disp = (double) k2i * (q * q) * d2;
-                vel  = vnorm2 * disp;
-            }
-            if (live) add(k2i, sqrt_pos((double) k2i), d2, P, disp, vel);
-        }
-    } else {  // the arithmetic of k_gen, position by position
-        EigAxis eax = {0, 0, 0.0}, eay = {0, 0, 0.0};
+    zdsweep::sweep_modes<PLAW, FAST>(g, J, T, ky, lG, x, act, z0, z1, false, [&](const SweepMode &m) {
+        const double d2 = FAST ? fma(m.dr, m.dr, m.di * m.di) : m.dr * m.dr + m.di * m.di;
+        double disp, vel;
         if constexpr (PLT) {
-            eax = eig_axis(g, eig_index_x(g, kx));
-            eay = eig_axis(g, ky);
-        }
-#pragma unroll 1
-        for (int z = z0; z < z1 && act; z++) {
-            int zs = z, xs = x;
-            bool cj = false, zero = false;
-            uint64_t r1 = 0, r2 = 0;
-            if (ky != 0) {
-                if (!g.phik) {
-                    r1 = zdpcg::output(s);
-                    const u128 s2 = zdpcg::step(s);
-                    r2 = zdpcg::output(s2);
-                    s  = zdpcg::apply(J.next[z == half], s2);
-                }
-            } else {  // "loser" positions take the conjugate of the winner's mode (zeldovich.cpp:485-503)
-                if (z > half) {
-                    zs = N - z;
-                    xs = x ? N - x : 0;
-                    cj = true;
-                } else if (z == 0) {
-                    if (x == 0)
-                        zero = true;
-                    else if (x > half) {
-                        xs = N - x;
-                        cj = true;
-                    }
-                }
-            }
-            const int kxm = xs > half ? xs - N : xs, kzm = zs > half ? zs - N : zs;  // generated mode
-            const int k2i = kxm * kxm + ky * ky + kzm * kzm;
-            const double k2v = (double) k2i * g.fundamental2;
-            if (zero || k2i == 0 || mode_is_zero(g, kxm, ky, kzm, k2v)) continue;
-            double P, ik2;
-            if (g.pk_tab) {  // {P(k), 1/k^2} by integer k^2
-                const double2 pv = g.pk_tab[k2i];
-                P   = pv.x;
-                ik2 = pv.y;
+            double e[4];
+            double f, rescale = 1.0, sx, sy, sz;
+            if constexpr (FAST) {
+                eigenmode_fast(g, m.kx, ky, m.kz, exy, eig_axis(g, eig_index_z(g, m.kz)), e);
+                f = (sqrt_pos(1. + 24 * e[3] * g.f_cluster) - 1) * .25;
+                if (g.qPLTrescale) rescale = fexp(g.ln_growth_ratio * (g.target_f - f), T);
+                sx = rescale * e[0], sy = rescale * e[1], sz = rescale * e[2];
             } else {
-                P   = pk_power<PLAW>(g, k2v);
-                ik2 = 1.0 / k2v;
-            }
-            double dr, di;
-            if (g.phik) {  // f_NL: D = phi_NG(k) M(k) (zeldovich.cpp:393-400); PhiK rows are this rank's row slots
-                const cplx ph  = g.phik[((long long) (ky >> lG) * N + zs) * N + xs];
-                const double M = g.fnl_M[k2i];
-                dr = ph.x * M;
-                di = ph.y * M;
-            } else {
-                if (ky == 0) {
-                    const u128 t = pk_advance(J, g.row_state[0], 2ULL * ((uint64_t) (kzm & 65535) * 65536ULL + (uint64_t) (kxm & 65535)) + 1ULL);
-                    r1 = zdpcg::output(t);
-                    r2 = zdpcg::output(zdpcg::step(t));
-                }
-                gauss_from_pk(g, P, r1, r2, dr, di);
-            }
-            const double d2 = dr * dr + di * di;
-            double disp, vel;
-            if constexpr (PLT) {
-                double e[4];
-                const EigAxis eaz = eig_axis(g, eig_index_z(g, kzm));
-                if (cj)  // mirrored source mode (ky = 0 plane only): its own x axis
-                    get_eigenmode_dev(g, kxm, ky, kzm, eig_axis(g, eig_index_x(g, kxm)), eay, eaz, e);
+                const EigAxis eaz = eig_axis(g, eig_index_z(g, m.kz));
+                if (m.cj)  // mirrored source mode (ky = 0 plane only): its own x axis
+                    get_eigenmode_dev(g, m.kx, ky, m.kz, eig_axis(g, eig_index_x(g, m.kx)), eay, eaz, e);
                 else
-                    get_eigenmode_dev(g, kxm, ky, kzm, eax, eay, eaz, e);
-                const double f = (sqrt(1. + 24 * e[3] * g.f_cluster) - 1) * .25;
-                double rescale = 1.0;
+                    get_eigenmode_dev(g, m.kx, ky, m.kz, eax, eay, eaz, e);
+                f = (sqrt(1. + 24 * e[3] * g.f_cluster) - 1) * .25;
                 if (g.qPLTrescale) rescale = exp(g.ln_growth_ratio * (g.target_f - f));
-                const double sx = rescale * e[0] * g.fundamental * ik2, sy = rescale * e[1] * g.fundamental * ik2,
-                             sz = rescale * e[2] * g.fundamental * ik2;
-                disp = (sx * sx + sy * sy + sz * sz) * d2;
-                vel  = f * f * disp;
-            } else {
-                const double q = g.fundamental * ik2;
-                disp = (double) k2i * (q * q) * d2;
-                vel  = vnorm2 * disp;
+                sx = rescale * e[0] * g.fundamental * m.ik2, sy = rescale * e[1] * g.fundamental * m.ik2, sz = rescale * e[2] * g.fundamental * m.ik2;
             }
-            add(k2i, sqrt((double) k2i), d2, P, disp, vel);
+            disp = (sx * sx + sy * sy + sz * sz) * d2;
+            vel  = f * f * disp;
+        } else {
+            const double q = g.fundamental * m.ik2;
+            disp = (double) m.k2i * (q * q) * d2;
+            vel  = vnorm2 * disp;
         }
-    }
+        if (m.live) add(m.k2i, FAST ? sqrt_pos((double) m.k2i) : sqrt((double) m.k2i), d2, m.P, disp, vel);
+    });
     flush();
     __syncthreads();
     for (int i = threadIdx.x; i < PK_WIN; i += PK_BX) {
@@ -303,7 +191,7 @@ __global__ __launch_bounds__(PK_BX) void k_pk_sweep(GenConst g, PkJumps J, int k
 }
 
 template <bool PLT, bool PLAW, bool FAST>
-int launch_pk_t(const GenConst &g, const PkJumps &J, int ky_first, int ky_stride, int nrows, int lG, int w, int nbins, double vnorm2,
+int launch_pk_t(const GenConst &g, const SweepJumps &J, int ky_first, int ky_stride, int nrows, int lG, int w, int nbins, double vnorm2,
                 unsigned long long *gcount, double *gsum, hipStream_t st) {
     if (nrows <= 0) return 0;
     const int zc = std::min(g.N, PK_ZC);
@@ -316,7 +204,7 @@ int launch_pk_t(const GenConst &g, const PkJumps &J, int ky_first, int ky_stride
 }
 
 template <bool FAST>
-int launch_pk(const GenConst &g, const PkJumps &J, int ky_first, int ky_stride, int nrows, int lG, int w, int nbins, double vnorm2,
+int launch_pk(const GenConst &g, const SweepJumps &J, int ky_first, int ky_stride, int nrows, int lG, int w, int nbins, double vnorm2,
               unsigned long long *gcount, double *gsum, hipStream_t st) {
     const bool plt = g.qPLT != 0, plaw = g.is_powerlaw != 0;
 #define PCASE(a, b) \
@@ -377,13 +265,7 @@ extern "C" int zd_plan_measure_power(zd_plan *pl, int32_t bin_width, int64_t nbi
     }
     unsigned long long *gcount = (unsigned long long *) buf.p;
     double *gsum = (double *) buf.p + nb;
-    PkJumps J;
-    for (int i = 0; i < PK_NBIT; i++) J.bit[i] = zdpcg::jump_map(((u128) 1) << i);
-    const u128 row = (u128) 2 * 65536, wrap = (u128) (65536 - pl->N);
-    J.next[0]      = zdpcg::jump_map(row - 1);
-    J.next[1]      = zdpcg::jump_map(row * (1 + wrap) - 1);
-    J.next_full[0] = zdpcg::jump_map(row);
-    J.next_full[1] = zdpcg::jump_map(row * (1 + wrap));
+    const SweepJumps J = zdsweep::make_sweep_jumps(pl->N);
     const int G = pl->nranks, rank = pl->rank, Hq = pl->Hq;  // rows ky = rank + G i, i < Hq
     const double vnorm2 = pl->ec.vnorm * pl->ec.vnorm;
     const bool fast = g.genf_tab && !g.phik && !g.qonemode;

@@ -35,6 +35,11 @@ struct Writer {
     int dens_fd = -1;
     size_t bytes_written = 0;
     double seconds = 0;
+    // ZD_SelfCheck: the sites (z, y, x), and the record / density the callback delivered at each of them
+    std::vector<int64_t> sites;
+    std::vector<unsigned char> site_rec;
+    std::vector<float> site_dens;
+    std::vector<int> site_seen;
 
     // first z stored in file `f`: smallest z with z*cpd/ppd == f   (output.cpp:208)
     int64_t first_z_of_file(int f) const {
@@ -60,6 +65,13 @@ struct Writer {
     static int callback(void *user, int64_t z, int64_t n, const void *records, const float *density) {
         Writer *w = (Writer *) user;
         const auto t0 = std::chrono::steady_clock::now();
+        for (size_t i = 0; i < w->site_seen.size(); i++) {
+            if (w->sites[3 * i] != z) continue;
+            const int64_t at = w->sites[3 * i + 1] * w->p.ppd + w->sites[3 * i + 2];
+            if (records) memcpy(w->site_rec.data() + i * w->recsize, (const unsigned char *) records + at * w->recsize, w->recsize);
+            if (density) w->site_dens[i] = density[at];
+            w->site_seen[i] = 1;
+        }
         if (records) {
             const int f = (int) (z * w->p.cpd / w->p.ppd);
             // with ZD_qoneslab only one plane is written; the reference appends it at offset 0
@@ -126,6 +138,89 @@ static int write_measured_power(const char *path, const zd_params &p, const zd_p
     return 0;
 }
 
+// ZD_SelfCheck = n.  THE SITES: a splitmix64 stream started at ZD_Seed gives three draws per site, (z, y, x) = draw mod PPD each, in that
+// order, site after site; site 1 then takes z = (z of site 0 + 1) mod PPD, so that for n >= 2 the sites lie on two different z residues
+// of every stream factor >= 2 (stream factors divide PPD); with ZD_qoneslab every site takes z = ZD_qoneslab.
+static std::vector<int64_t> self_check_sites(const zd_params &p, int n) {
+    uint64_t state = (uint64_t) p.seed;
+    auto next = [&]() {
+        uint64_t v = (state += 0x9E3779B97F4A7C15ULL);
+        v = (v ^ (v >> 30)) * 0xBF58476D1CE4E5B9ULL;
+        v = (v ^ (v >> 27)) * 0x94D049BB133111EBULL;
+        return v ^ (v >> 31);
+    };
+    std::vector<int64_t> s(3 * (size_t) n);
+    for (auto &v : s) v = (int64_t) (next() % (uint64_t) p.ppd);
+    if (n >= 2) s[3] = (s[0] + 1) % p.ppd;
+    if (p.qoneslab >= 0)
+        for (int i = 0; i < n; i++) s[3 * i] = p.qoneslab;
+    return s;
+}
+
+// the delivered records at the sites against zd_direct_sum; returns non-zero if the check fails or cannot be made
+static int self_check(const Writer &w, const zd_param_strings &s, const zd_pk &pk, const double *eig, int64_t eig_ppd) {
+    const zd_params &p = w.p;
+    const int n = (int) w.site_seen.size();
+    std::vector<double> sum(7 * (size_t) n), rec(7 * (size_t) n, NAN);
+    if (zd_direct_sum(&p, &pk, eig, eig_ppd, n, w.sites.data(), sum.data())) return 1;
+    const bool have_rec = w.recsize > 0, have_vel = p.icformat == ZD_FMT_RVZEL || p.icformat == ZD_FMT_RVDOUBLEZEL, have_dens = p.qdensity != 0;
+    double qmax = 0, dmax = 0, worst = 0, worst_dens = 0;
+    for (int i = 0; i < n; i++) {
+        for (int j = 0; j < 3; j++) qmax = std::max(qmax, fabs(sum[7 * i + j]));
+        dmax = std::max(dmax, fabs(sum[7 * i + 6]));
+    }
+    for (int i = 0; i < n; i++) {
+        if (!w.site_seen[i]) {
+            fprintf(stderr, "self-check: plane z = %lld was never delivered\n", (long long) w.sites[3 * i]);
+            return 1;
+        }
+        const unsigned char *r = w.site_rec.data() + (size_t) i * w.recsize;
+        // records hold (z, y, x) components: d[3] (+ v[3]) behind the 8-byte lattice index, ZelSimple d[3] alone; float32 or float64
+        const bool f64 = p.icformat == ZD_FMT_RVDOUBLEZEL || p.icformat == ZD_FMT_ZEL;
+        const size_t off = p.icformat == ZD_FMT_ZELSIMPLE ? 0 : 8;
+        for (int j = 0; have_rec && j < (have_vel ? 6 : 3); j++) {
+            double v;
+            if (f64) {
+                memcpy(&v, r + off + 8 * j, 8);
+            } else {
+                float f;
+                memcpy(&f, r + off + 4 * j, 4);
+                v = f;
+            }
+            const int col = j < 3 ? 2 - j : 3 + (5 - j);  // (qz, qy, qx, vz, vy, vx) -> qx, qy, qz, vx, vy, vz
+            rec[7 * i + col] = v;
+            worst = std::max(worst, fabs(v - sum[7 * i + col]) / qmax);
+        }
+        if (have_dens) {  // the density plane is float32 in every format: the direct sum is rounded to it before the comparison
+            rec[7 * i + 6] = w.site_dens[i];
+            worst_dens = std::max(worst_dens, fabs((double) w.site_dens[i] - (double) (float) sum[7 * i + 6]) / dmax);
+        }
+    }
+    if (s.SelfCheck_filename[0]) {
+        FILE *f = fopen(s.SelfCheck_filename, "w");
+        if (!f) {
+            fprintf(stderr, "Could not open self-check file \"%s\"\n", s.SelfCheck_filename);
+            return 1;
+        }
+        fprintf(f, "# z y x | record: qx qy qz vx vy vz density (nan: not delivered) | direct sum: qx qy qz vx vy vz density\n");
+        for (int i = 0; i < n; i++) {
+            fprintf(f, "%lld %lld %lld", (long long) w.sites[3 * i], (long long) w.sites[3 * i + 1], (long long) w.sites[3 * i + 2]);
+            for (int j = 0; j < 7; j++) fprintf(f, " %.17g", rec[7 * i + j]);
+            for (int j = 0; j < 7; j++) fprintf(f, " %.17g", sum[7 * i + j]);
+            fprintf(f, "\n");
+        }
+        fclose(f);
+    }
+    fprintf(stderr, "self-check: %d sites, max |record - direct sum| / max|q| = %.3g", n, worst);
+    if (have_dens) fprintf(stderr, ", max |density - direct sum| / max|density| = %.3g", worst_dens);
+    fprintf(stderr, " (ZD_SelfCheck_tol = %g)\n", s.SelfCheck_tol);
+    if (!(worst <= s.SelfCheck_tol) || !(worst_dens <= s.SelfCheck_tol)) {
+        fprintf(stderr, "self-check FAILED: the delivered records differ from the direct summation over the modes\n");
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char *argv[]) {
     if (argc != 2) {
         fprintf(stderr, "Usage: %s param_file\n", argv[0]);
@@ -161,6 +256,12 @@ int main(int argc, char *argv[]) {
     static const int recsizes[4] = {32, 32, 56, 12};
     w.recsize     = p.qdensity == 2 ? 0 : recsizes[p.icformat];
     w.plane_bytes = (int64_t) p.ppd * p.ppd * w.recsize;
+    if (s.SelfCheck > 0) {
+        w.sites = self_check_sites(p, s.SelfCheck);
+        w.site_rec.assign((size_t) s.SelfCheck * w.recsize, 0);
+        w.site_dens.assign(s.SelfCheck, 0.f);
+        w.site_seen.assign(s.SelfCheck, 0);
+    }
     if (p.qdensity) {  // InitOutputBuffers: output.cpp:282-288; "density{:d}" is an fmt pattern on ppd
         std::string name = s.density_filename;
         const size_t pos = name.find("{:d}");
@@ -204,6 +305,7 @@ int main(int argc, char *argv[]) {
                 (int) (p.boxsize / (2 * fabs(st.max_disp[2]))));
     }
     if (s.Pk_measured_filename[0] && write_measured_power(s.Pk_measured_filename, p, pk, eig, eig_ppd)) exit(1);
+    if (s.SelfCheck > 0 && self_check(w, s, pk, eig, eig_ppd)) exit(1);
     w.close_all();
     fprintf(stderr, "WriteParticlesSlab took %.3g sec to write %.3g MB ==> %.3g MB/sec\n", w.seconds,
             w.bytes_written / 1e6, w.bytes_written / 1e6 / (w.seconds > 0 ? w.seconds : 1e-9));
