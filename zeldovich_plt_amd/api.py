@@ -88,7 +88,7 @@ EXPORTED_SYMBOLS = [
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
-                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route", "zd_test_lpt2_coefficients"]
+                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route", "zd_test_lpt2_coefficients", "zd_test_live_handles"]
 STORE_MODES = {"auto": 0, "reference": 1, "packed": 2, "fields": 3}  # zd_params.store_mode (ZD_STORE_*)
 
 _lib = None
@@ -139,6 +139,8 @@ def _load(path, testing):
         L.zd_test_poison.restype = None
         L.zd_test_lpt2_coefficients.argtypes = [C.POINTER(ZdParams), vp]
         L.zd_test_lpt2_coefficients.restype = None
+        L.zd_test_live_handles.argtypes = []
+        L.zd_test_live_handles.restype = i64
     L.zd_choose_stream_factor.argtypes = [C.POINTER(ZdParams), C.c_int, i64]
     L.zd_choose_pass_groups.argtypes = [C.POINTER(ZdParams), C.c_int, i64, C.POINTER(i32), C.POINTER(i32)]
     L.zd_plan_create.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, C.c_int, C.c_int, C.POINTER(vp)]

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <cmath>
@@ -31,6 +32,12 @@ using zdpcg::u128;
 using zd::is_pow2;
 using zd::Route;
 using zd::route;
+using zdown::DevBuf;
+using zdown::Event;
+using zdown::PinnedBuf;
+using zdown::PlanPtr;
+using zdown::Stream;
+using zdown::upload;
 
 #define HIPCHECK(call)                                                                               \
     do {                                                                                             \
@@ -102,7 +109,7 @@ std::vector<cplx> make_twiddles(int n) {
 
 // Bluestein tables of a length-n transform on the engine of size M = 2^m >= 2n - 1 (zd_kernels_any.hip): c_m = exp(i pi m^2/n)
 // with m^2 reduced mod 2n in integers, and the forward DFT_M of b_m = conj(c_m), |m| < n, wrapped (long double radix-2)
-int any_make_tab(int n, zd::AnyTab *tab, cplx **d_bufs) {
+int any_make_tab(int n, zd::AnyTab *tab, DevBuf<cplx> *d_bufs) {
     const int M = zd::any_engine_size(n);
     const long double PI = 3.14159265358979323846264338327950288L;
     std::vector<cplx> chirp(n), tw = make_twiddles(M);
@@ -145,10 +152,8 @@ int any_make_tab(int n, zd::AnyTab *tab, cplx **d_bufs) {
     std::vector<cplx> fb(M);
     for (int i = 0; i < M; i++) fb[i] = cplx{(double) br[i], (double) bi[i]};
     const std::vector<cplx> *src[3] = {&tw, &chirp, &fb};
-    for (int i = 0; i < 3; i++) {
-        if (hipMalloc((void **) &d_bufs[i], sizeof(cplx) * src[i]->size()) != hipSuccess) return 1;
-        if (hipMemcpy(d_bufs[i], src[i]->data(), sizeof(cplx) * src[i]->size(), hipMemcpyHostToDevice) != hipSuccess) return 1;
-    }
+    for (int i = 0; i < 3; i++)
+        if (upload(d_bufs[i], *src[i]) != hipSuccess) return 1;
     tab->n     = n;
     tab->M     = M;
     tab->invM  = 1.0 / (double) M;
@@ -614,81 +619,67 @@ static int any_lines(const zd_plan *pl, void *data, long long pitch, long long n
 // phi_mode 1: first f_NL pass (one array holding phi = D/M); phik != NULL: second pass (D = phik * M).  ZD_q2LPT: phi_mode 2 = the
 // plan of the second-order round's gradient passes; phik != NULL with phi_mode 0 = the final pass, phik holding the source S(k)
 static int plan_create_ex(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
-                          int phi_mode, const cplx *phik, zd_plan **out);
+                          int phi_mode, const cplx *phik, PlanPtr &out);
+// a plan that was made goes to a caller of the C ABI; *out is left alone otherwise
+static int hand_over(int rc, PlanPtr &pl, zd_plan **out) {
+    if (!rc) *out = pl.release();
+    return rc;
+}
 
 // f_NL: phi field -> local transform phi + f_NL phi^2 -> Fourier space again (zeldovich.cpp:945-960, 699-790): the first
 // ZeldovichZ / ZeldovichXY_Phi round of the reference, run once; *d_phik = PhiK[ky][kz][x] for the half-space rows (owned
-// by the caller).  One rank: the forward z transform needs every plane resident.
-static int make_phik(const zd_params *p, const zd_pk *pk, cplx **d_phik) {
+// by the caller, untouched on failure).  One rank: the forward z transform needs every plane resident.
+static int make_phik(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d_phik) {
     const int64_t N  = p->ppd;
     zd_params pp     = *p;
     pp.stream_factor = 1;
     pp.qPLT          = 0;  // the phi pass never reaches the displacement algebra
-    zd_plan *ph      = nullptr;
-    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 1, nullptr, &ph)) return 1;
-    void *d_phi = nullptr;
-    int frc     = 1;
-    *d_phik     = nullptr;
+    PlanPtr plan;
+    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 1, nullptr, plan)) return 1;
+    zd_plan *ph = plan.get();
+    DevBuf<void> d_phi;
+    DevBuf<cplx> d_out;  // PhiK, handed to the caller at the end: every early return frees it
     // composite transforms (fnl_np2): phi is a real field, so the planes keep the half-space rows ky < N/2 only (k_refq_yphi rebuilds
     // a column from its half) — 8 N^3 bytes beside PhiK's 8 N^3 where the full store held 16 N^3
     ph->phi_half = ph->d_twr_n != nullptr && ph->jobs.n == 1 && ph->R == 1;
     const int64_t phi_bytes = ph->phi_half ? (N / 2) * N * ph->AL.pitch * 16 : zd_plan_exchange_bytes(ph);
-    do {
-        if (zd_store_alloc(&d_phi, (size_t) phi_bytes) != hipSuccess
-            || zd_store_alloc((void **) d_phik, (size_t) (N / 2) * N * N * 16) != hipSuccess) {
-            fprintf(stderr, "zeldovich_hip: f_NL needs %.1f GB of HBM for the phi field at PPD %lld\n",
-                    (phi_bytes + (N / 2) * N * N * 16) / 1e9, (long long) N);
-            break;
-        }
-        fprintf(stderr, "Generating phi field\n");
-        if (zd_plan_stage_z(ph, 0, d_phi, 0)) break;
-        if (ph->phi_half) {  // x inverse, y inverse + phi + f_NL phi^2 + y, x, then z into PhiK (conjugated: see below)
-            const long long pitch = ph->AL.pitch, plane = (long long) (N / 2) * pitch;
-            if (any_lines(ph, d_phi, pitch, (long long) N * (N / 2), 0)) break;
-            if (zd::launch_refq_yphi((int) N, ph->d_twr_n, d_phi, pitch, (int) N, p->f_NL, 0)) break;
-            if (any_lines(ph, d_phi, pitch, (long long) N * (N / 2), 0)) break;
-            if (zd::launch_refq_cols_oop((int) N, ph->d_twr_n, d_phi, pitch, plane, *d_phik, N * N, N, (int) N, (int) (N / 2), true, 0)) break;
-            if (hipDeviceSynchronize() != hipSuccess) break;
-            frc = 0;
-            break;
-        }
-        if (zd_plan_stage_y(ph, d_phi, 0)) break;
-        if (ph->any) {  // reference-array PPDs: x inverse, phi + f_NL phi^2, then the forward 3-D transform of that REAL field as the
-                        // conjugate of its inverse transform (x, y, z in place; conjugated while PhiK is laid out).  The lines go
-                        // through the composite transforms on the composite grids (fnl_np2), else as convolutions.
-            const long long plane = (long long) N * ph->AL.pitch;
-            if (any_lines(ph, d_phi, ph->AL.pitch, (long long) N * N, 0)) break;
-            if (zd::launch_any_phi_nl(ph->AL, p->f_NL, d_phi, 0)) break;
-            if (any_lines(ph, d_phi, ph->AL.pitch, (long long) N * N, 0)) break;
-            if (any_cols(ph, false, d_phi, plane, ph->AL.pitch, (int) N, (int) N, -1, 0)) break;
-            if (any_cols(ph, false, d_phi, ph->AL.pitch, plane, (int) N, (int) (N / 2), -1, 0)) break;  // along z, rows ky < N/2
-            if (zd::launch_any_phik(ph->AL, d_phi, *d_phik, 0)) break;
-            if (hipDeviceSynchronize() != hipSuccess) break;
-            frc = 0;
-            break;
-        }
+    if (d_phi.store_alloc((size_t) phi_bytes) != hipSuccess || d_out.store_alloc((size_t) (N / 2) * N * N) != hipSuccess) {
+        fprintf(stderr, "zeldovich_hip: f_NL needs %.1f GB of HBM for the phi field at PPD %lld\n",
+                (phi_bytes + (N / 2) * N * N * 16) / 1e9, (long long) N);
+        return 1;
+    }
+    fprintf(stderr, "Generating phi field\n");
+    if (zd_plan_stage_z(ph, 0, d_phi, 0)) return 1;
+    if (ph->phi_half) {  // x inverse, y inverse + phi + f_NL phi^2 + y, x, then z into PhiK (conjugated: see below)
+        const long long pitch = ph->AL.pitch, plane = (long long) (N / 2) * pitch;
+        if (any_lines(ph, d_phi, pitch, (long long) N * (N / 2), 0)) return 1;
+        if (zd::launch_refq_yphi((int) N, ph->d_twr_n, d_phi, pitch, (int) N, p->f_NL, 0)) return 1;
+        if (any_lines(ph, d_phi, pitch, (long long) N * (N / 2), 0)) return 1;
+        if (zd::launch_refq_cols_oop((int) N, ph->d_twr_n, d_phi, pitch, plane, d_out, N * N, N, (int) N, (int) (N / 2), true, 0)) return 1;
+    } else if (zd_plan_stage_y(ph, d_phi, 0)) {
+        return 1;
+    } else if (ph->any) {  // reference-array PPDs: x inverse, phi + f_NL phi^2, then the forward 3-D transform of that REAL field as the
+                           // conjugate of its inverse transform (x, y, z in place; conjugated while PhiK is laid out).  The lines go
+                           // through the composite transforms on the composite grids (fnl_np2), else as convolutions.
+        const long long plane = (long long) N * ph->AL.pitch;
+        if (any_lines(ph, d_phi, ph->AL.pitch, (long long) N * N, 0)) return 1;
+        if (zd::launch_any_phi_nl(ph->AL, p->f_NL, d_phi, 0)) return 1;
+        if (any_lines(ph, d_phi, ph->AL.pitch, (long long) N * N, 0)) return 1;
+        if (any_cols(ph, false, d_phi, plane, ph->AL.pitch, (int) N, (int) N, -1, 0)) return 1;
+        if (any_cols(ph, false, d_phi, ph->AL.pitch, plane, (int) N, (int) (N / 2), -1, 0)) return 1;  // along z, rows ky < N/2
+        if (zd::launch_any_phik(ph->AL, d_phi, d_out, 0)) return 1;
+    } else {
         int lN = 0;
         while ((1 << lN) < (int) N) lN++;
-        if (zd::launch_fnl_stage(0, ph->S, p->f_NL, ph->d_twN, d_phi, nullptr, (int) N, lN, 0)) break;
-        if (zd::launch_fnl_stage(1, ph->S, p->f_NL, ph->d_twN, d_phi, nullptr, (int) N, lN, 0)) break;
-        if (zd::launch_fnl_stage(2, ph->S, p->f_NL, ph->d_twN, d_phi, *d_phik, (int) N, lN, 0)) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        frc = 0;
-    } while (0);
-    hipFree(d_phi);
-    zd_plan_destroy(ph);
-    if (frc) {
-        hipFree(*d_phik);
-        *d_phik = nullptr;
+        if (zd::launch_fnl_stage(0, ph->S, p->f_NL, ph->d_twN, d_phi, nullptr, (int) N, lN, 0)) return 1;
+        if (zd::launch_fnl_stage(1, ph->S, p->f_NL, ph->d_twN, d_phi, nullptr, (int) N, lN, 0)) return 1;
+        if (zd::launch_fnl_stage(2, ph->S, p->f_NL, ph->d_twN, d_phi, d_out, (int) N, lN, 0)) return 1;
     }
-    return frc;
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    d_phik = std::move(d_out);
+    return 0;
 }
 
-// ZD_q2LPT: the second-order round (definition and shape: zd_kernels_lpt2.hip), run once; *d_sk = S(k)[ky][kz][x] for the half-space
-// rows, already scaled by N^-3 (owned by the caller).  Four gradient passes over one one-array store — generator, z and y stages of
-// the plan, then the x lines into the real accumulator — and the forward transforms of the f_NL phi round.  The accumulator is freed
-// before S(k) is allocated: the peak is lpt2_round_bytes.
-static int make_lpt2_source_dealiased(const zd_params *p, const zd_pk *pk, cplx **d_sk);
 // the round's peak against the free memory, asked before anything is built (the figure is the message)
 static int lpt2_round_fits(const zd_params *p, int64_t free_bytes) {
     if (lpt2_round_bytes(p) <= free_bytes) return 1;
@@ -696,55 +687,10 @@ static int lpt2_round_fits(const zd_params *p, int64_t free_bytes) {
             p->lpt2_dealias ? " with ZD_2LPT_dealias = 1" : "", lpt2_round_bytes(p) / 1e9, (long long) p->ppd, free_bytes / 1e9);
     return 0;
 }
-static int make_lpt2_source(const zd_params *p, const zd_pk *pk, cplx **d_sk) {
-    if (p->lpt2_dealias) return make_lpt2_source_dealiased(p, pk, d_sk);
-    const int64_t N  = p->ppd;
-    zd_params pp     = *p;
-    pp.stream_factor = 1;   // the forward z transform needs every plane of a row
-    pp.qoneslab      = -1;  // (the source needs the whole field whatever is delivered)
-    zd_plan *ph      = nullptr;
-    *d_sk            = nullptr;
-    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 2, nullptr, &ph)) return 1;
-    void *d_grad = nullptr, *d_acc = nullptr;
-    int frc      = 1;
-    do {
-        if (zd_store_alloc(&d_grad, (size_t) zd_plan_exchange_bytes(ph)) != hipSuccess
-            || zd_store_alloc(&d_acc, (size_t) N * N * N * sizeof(double)) != hipSuccess) {
-            fprintf(stderr, "zeldovich_hip: ZD_q2LPT needs %.1f GB of HBM for the second-order round at PPD %lld\n",
-                    lpt2_round_bytes(p) / 1e9, (long long) N);
-            break;
-        }
-        int pass = 1;
-        for (; pass <= 4; pass++) {
-            ph->g.lpt2 = pass;
-            if (zd_plan_stage_z(ph, 0, d_grad, 0) || zd_plan_stage_y(ph, d_grad, 0)) break;
-            if (zd::launch_lpt2_xsrc(ph->S, pass, ph->d_twN, d_grad, (double *) d_acc, (int) N, 0)) break;
-        }
-        if (pass <= 4) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        hipFree(d_acc);
-        d_acc = nullptr;
-        if (zd_store_alloc((void **) d_sk, (size_t) lpt2_sk_bytes(N)) != hipSuccess) {
-            fprintf(stderr, "zeldovich_hip: ZD_q2LPT needs %.1f GB of HBM for the second-order source at PPD %lld\n",
-                    lpt2_sk_bytes(N) / 1e9, (long long) N);
-            break;
-        }
-        int lN = 0;
-        while ((1 << lN) < (int) N) lN++;
-        if (zd::launch_fnl_stage(1, ph->S, 0.0, ph->d_twN, d_grad, nullptr, (int) N, lN, 0)) break;
-        if (zd::launch_fnl_stage(2, ph->S, 0.0, ph->d_twN, d_grad, *d_sk, (int) N, lN, 0)) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        frc = 0;
-    } while (0);
-    hipFree(d_acc);
-    hipFree(d_grad);
-    zd_plan_destroy(ph);
-    if (frc) {
-        hipFree(*d_sk);
-        *d_sk = nullptr;
-    }
-    return frc;
-}
+// ZD_q2LPT: the second-order round (definition and shape: zd_kernels_lpt2.hip), run once; d_sk = S(k)[ky][kz][x] for the half-space
+// rows, already scaled by N^-3 (handed to the caller).  Four gradient passes over one one-array store — generator, z and y stages of
+// the plan, then the x lines into the real accumulator — and the forward transforms of the f_NL phi round.  The accumulator is freed
+// before S(k) is allocated: the peak is lpt2_round_bytes.
 // ZD_2LPT_dealias = 1 (step 2' of the definition): the same round on the lattice of M = 3 N / 2 points per side.  The plan of the gradient
 // passes is a plan AT M — ZD_k_cutoff x 1.5, the same box, the same seed: the counter-addressed draws and the zero rule give exactly the
 // modes of the N run, at their signed wavenumbers — on a one-array store [z][y][x] of the reference-array family, every line through
@@ -752,69 +698,66 @@ static int make_lpt2_source(const zd_params *p, const zd_pk *pk, cplx **d_sk) {
 // the x transform; the y columns |kx| < N/2 follow in place, and the z lines of the columns |kx| < N/2, 0 <= ky < N/2 go, truncated
 // to |kz| < N/2 and conjugated (three inverse transforms of a real field are the conjugate of its forward transform), straight
 // into S(k)[ky][kz][x] of the N layout.
-static int make_lpt2_source_dealiased(const zd_params *p, const zd_pk *pk, cplx **d_sk) {
-    const int64_t N = p->ppd, M = zd::lpt2_dealias_lattice(N);
-    *d_sk           = nullptr;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || !lpt2_round_fits(p, (int64_t) free_b)) return 1;
-    }
+static int make_lpt2_source(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d_sk) {
+    const bool dq   = p->lpt2_dealias != 0;
+    const int64_t N = p->ppd, M = dq ? zd::lpt2_dealias_lattice(N) : N;  // points per side of the round's lattice
+    size_t free_b = 0, total_b = 0;
+    if (dq && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || !lpt2_round_fits(p, (int64_t) free_b))) return 1;
     zd_params pp     = *p;
-    pp.ppd           = M;
-    pp.k_cutoff      = p->k_cutoff * 1.5;
-    pp.nyquist       = p->nyquist * 1.5;  // (k2_cutoff = nyquist^2 / k_cutoff^2 may move by an ulp: it decides differently only for an integer
-                                          // |k|^2 ON the cut, and at k_cutoff = 1, 2 that is |k|^2 = kmax^2 = 4^a, the modes (kmax, 0, 0) the
-                                          // |k_i| == kmax rule kills anyway; kmax itself is checked below)
-    pp.lpt2_dealias  = 0;
-    pp.stream_factor = 1;
-    pp.qoneslab      = -1;
-    zd_plan *ph      = nullptr;
-    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 2, nullptr, &ph)) return 1;
-    void *d_grad = nullptr, *d_acc = nullptr;
-    int frc      = 1;
-    do {
-        if (!ph->d_twr_n || ph->N != M || ph->g.kmax != (int) ((double) (N / 2) * (1.0 / p->k_cutoff) + .5)) {
-            fprintf(stderr, "zeldovich_hip: ZD_2LPT_dealias: the plan on the %lld lattice does not carry the modes of PPD %lld\n", (long long) M,
-                    (long long) N);
-            break;
-        }
-        if (zd_store_alloc(&d_grad, (size_t) zd_plan_exchange_bytes(ph)) != hipSuccess
-            || zd_store_alloc(&d_acc, (size_t) M * M * M * sizeof(double)) != hipSuccess) {
-            fprintf(stderr, "zeldovich_hip: ZD_q2LPT with ZD_2LPT_dealias = 1 needs %.1f GB of HBM for the second-order round at PPD %lld\n",
-                    lpt2_round_bytes(p) / 1e9, (long long) N);
-            break;
-        }
-        const long long pitch = ph->AL.pitch, plane = M * pitch;
-        int pass = 1;
-        for (; pass <= 4; pass++) {
-            ph->g.lpt2 = pass;
-            if (zd_plan_stage_z(ph, 0, d_grad, 0) || zd_plan_stage_y(ph, d_grad, 0)) break;
-            if (zd::launch_lpt2q_xsrc((int) M, ph->d_twr_n, pass, d_grad, pitch, M * M, (double *) d_acc, 0)) break;
-        }
-        if (pass <= 4) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        hipFree(d_acc);
-        d_acc = nullptr;
-        if (zd_store_alloc((void **) d_sk, (size_t) lpt2_sk_bytes(N)) != hipSuccess) {
-            fprintf(stderr, "zeldovich_hip: ZD_q2LPT needs %.1f GB of HBM for the second-order source at PPD %lld\n",
-                    lpt2_sk_bytes(N) / 1e9, (long long) N);
-            break;
-        }
-        // y columns of the planes, only those that are kept: x = kx in [0, N/2) and x = M + kx, kx in (-N/2, 0)
-        if (zd::launch_refq_cols((int) M, ph->d_twr_n, d_grad, plane, pitch, (int) (N / 2), (int) M, -1, 0)) break;
-        if (zd::launch_refq_cols((int) M, ph->d_twr_n, (cplx *) d_grad + (M - N / 2 + 1), plane, pitch, (int) (N / 2 - 1), (int) M, -1, 0)) break;
-        if (zd::launch_lpt2q_zsrc((int) M, (int) N, ph->d_twr_n, d_grad, pitch, *d_sk, 0)) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        frc = 0;
-    } while (0);
-    hipFree(d_acc);
-    hipFree(d_grad);
-    zd_plan_destroy(ph);
-    if (frc) {
-        hipFree(*d_sk);
-        *d_sk = nullptr;
+    pp.stream_factor = 1;   // the forward z transform needs every plane of a row
+    pp.qoneslab      = -1;  // (the source needs the whole field whatever is delivered)
+    if (dq) {
+        pp.ppd          = M;
+        pp.k_cutoff     = p->k_cutoff * 1.5;
+        pp.nyquist      = p->nyquist * 1.5;  // (k2_cutoff = nyquist^2 / k_cutoff^2 may move by an ulp: it decides differently only for an integer
+                                             // |k|^2 ON the cut, and at k_cutoff = 1, 2 that is |k|^2 = kmax^2 = 4^a, the modes (kmax, 0, 0) the
+                                             // |k_i| == kmax rule kills anyway; kmax itself is checked below)
+        pp.lpt2_dealias = 0;
     }
-    return frc;
+    PlanPtr plan;
+    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 2, nullptr, plan)) return 1;
+    zd_plan *ph = plan.get();
+    if (dq && (!ph->d_twr_n || ph->N != M || ph->g.kmax != (int) ((double) (N / 2) * (1.0 / p->k_cutoff) + .5))) {
+        fprintf(stderr, "zeldovich_hip: ZD_2LPT_dealias: the plan on the %lld lattice does not carry the modes of PPD %lld\n", (long long) M,
+                (long long) N);
+        return 1;
+    }
+    DevBuf<cplx> d_grad, d_out;  // d_out: S(k), handed to the caller at the end: every early return frees it
+    DevBuf<double> d_acc;
+    if (d_grad.store_alloc((size_t) zd_plan_exchange_bytes(ph) / sizeof(cplx)) != hipSuccess || d_acc.store_alloc((size_t) M * M * M) != hipSuccess) {
+        fprintf(stderr, "zeldovich_hip: ZD_q2LPT%s needs %.1f GB of HBM for the second-order round at PPD %lld\n",
+                dq ? " with ZD_2LPT_dealias = 1" : "", lpt2_round_bytes(p) / 1e9, (long long) N);
+        return 1;
+    }
+    const long long pitch = ph->AL.pitch, plane = M * pitch;  // (the de-aliased round's store)
+    for (int pass = 1; pass <= 4; pass++) {
+        ph->g.lpt2 = pass;
+        if (zd_plan_stage_z(ph, 0, d_grad, 0) || zd_plan_stage_y(ph, d_grad, 0)) return 1;
+        if (dq ? zd::launch_lpt2q_xsrc((int) M, ph->d_twr_n, pass, d_grad, pitch, M * M, d_acc, 0)
+               : zd::launch_lpt2_xsrc(ph->S, pass, ph->d_twN, d_grad, d_acc, (int) N, 0))
+            return 1;
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    d_acc.reset();
+    if (d_out.store_alloc((size_t) lpt2_sk_bytes(N) / sizeof(cplx)) != hipSuccess) {
+        fprintf(stderr, "zeldovich_hip: ZD_q2LPT needs %.1f GB of HBM for the second-order source at PPD %lld\n",
+                lpt2_sk_bytes(N) / 1e9, (long long) N);
+        return 1;
+    }
+    if (dq) {
+        // y columns of the planes, only those that are kept: x = kx in [0, N/2) and x = M + kx, kx in (-N/2, 0)
+        if (zd::launch_refq_cols((int) M, ph->d_twr_n, d_grad, plane, pitch, (int) (N / 2), (int) M, -1, 0)) return 1;
+        if (zd::launch_refq_cols((int) M, ph->d_twr_n, d_grad + (M - N / 2 + 1), plane, pitch, (int) (N / 2 - 1), (int) M, -1, 0)) return 1;
+        if (zd::launch_lpt2q_zsrc((int) M, (int) N, ph->d_twr_n, d_grad, pitch, d_out, 0)) return 1;
+    } else {
+        int lN = 0;
+        while ((1 << lN) < (int) N) lN++;
+        if (zd::launch_fnl_stage(1, ph->S, 0.0, ph->d_twN, d_grad, nullptr, (int) N, lN, 0)) return 1;
+        if (zd::launch_fnl_stage(2, ph->S, 0.0, ph->d_twN, d_grad, d_out, (int) N, lN, 0)) return 1;
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    d_sk = std::move(d_out);
+    return 0;
 }
 // a ZD_q2LPT job the route takes for this call (the refusal printed otherwise), asked BEFORE the second-order round is run
 static int lpt2_route_check(const zd_params *p, int nranks, int rank) {
@@ -829,14 +772,17 @@ static zd::StoreLayout layout_for_chunks(const zd_plan *pl, int chunk_planes);
 static zd::AnyChunks any_chunks(const zd_plan *pl, int chunk_planes);
 
 // twiddles of a composite transform (zd_fft_q.h) of length len = P * Q: exp(2 pi i k / P) | exp(2 pi i k / len) | exp(2 pi i k / Q)
-static int upload_twq(int len, cplx **dst) {
+static std::vector<cplx> make_twq(int len) {  // (empty: no such transform)
     int P = 0, Q = 0;
-    if (!zd::np2_split(len, &P, &Q)) return 1;
+    if (!zd::np2_split(len, &P, &Q)) return {};
     std::vector<cplx> t = make_twiddles(P), b = make_twiddles(len), c = make_twiddles(Q);
     t.insert(t.end(), b.begin(), b.end());
     t.insert(t.end(), c.begin(), c.end());
-    if (hipMalloc((void **) dst, sizeof(cplx) * t.size()) != hipSuccess) return 1;
-    return hipMemcpy(*dst, t.data(), sizeof(cplx) * t.size(), hipMemcpyHostToDevice) != hipSuccess;
+    return t;
+}
+static int upload_twq(int len, DevBuf<cplx> &dst) {
+    const std::vector<cplx> t = make_twq(len);
+    return t.empty() || upload(dst, t) != hipSuccess;
 }
 
 // ---- f_NL on several ranks (zd_multi.cpp): the plans of the phi round and of the main pass, and the stages of the phi round
@@ -845,11 +791,13 @@ int zd_plan_create_phi(const zd_params *p, const zd_pk *pk, int rank, int nranks
     zd_params pp     = *p;
     pp.stream_factor = 1;  // the forward z transform needs every plane of a row: one pass
     pp.qPLT          = 0;
-    return plan_create_ex(&pp, pk, nullptr, 0, rank, nranks, 1, nullptr, out);
+    PlanPtr pl;
+    return hand_over(plan_create_ex(&pp, pk, nullptr, 0, rank, nranks, 1, nullptr, pl), pl, out);
 }
 int zd_plan_create_phik(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks, const void *d_phik,
                         zd_plan **out) {
-    return plan_create_ex(p, pk, eig, eig_ppd, rank, nranks, 0, (const cplx *) d_phik, out);
+    PlanPtr pl;
+    return hand_over(plan_create_ex(p, pk, eig, eig_ppd, rank, nranks, 0, (const cplx *) d_phik, pl), pl, out);
 }
 // planes [0, nplanes) of a ring slot with `chunk_planes` planes per chunk: inverse y, x (inverse, phi + f_NL phi^2, forward),
 // forward y — ZeldovichXY_Phi (zeldovich.cpp:699-790)
@@ -883,29 +831,21 @@ int zd_plan_phi_zfwd(zd_plan *pl, void *d_store, void *d_phik, void *hip_stream)
 
 int zd_plan_create(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
                    zd_plan **out) {
-    if (p->q2LPT) {  // the second-order round runs here, once; the plan owns S(k) and its Z stages read it beside their draws
-        cplx *d_sk = nullptr;
-        if (lpt2_route_check(p, nranks, rank) || make_lpt2_source(p, pk, &d_sk)) return 1;
-        if (plan_create_ex(p, pk, eig, eig_ppd, rank, nranks, 0, d_sk, out)) {
-            hipFree(d_sk);
+    PlanPtr pl;
+    DevBuf<cplx> d_phik;  // PhiK or S(k): the round runs here, once; the plan owns the result and its Z stages read it beside their draws
+    if (p->q2LPT) {
+        if (lpt2_route_check(p, nranks, rank) || make_lpt2_source(p, pk, d_phik)) return 1;
+    } else if (p->f_NL != 0.) {  // the phi round; the Z stages read D = PhiK * M
+        if (nranks != 1) {
+            fprintf(stderr, "zeldovich_hip: ZD_f_NL != 0 runs on one rank (the forward z transform of the phi field needs every plane)\n");
             return 1;
         }
-        (*out)->d_phik_owned = d_sk;
-        return 0;
+        if (make_phik(p, pk, d_phik)) return 1;
+        rank = 0;
     }
-    if (p->f_NL == 0.) return plan_create_ex(p, pk, eig, eig_ppd, rank, nranks, 0, nullptr, out);
-    // ZD_f_NL: the phi round runs here, once; the plan owns PhiK and its Z stages read D = PhiK * M
-    if (nranks != 1) {
-        fprintf(stderr, "zeldovich_hip: ZD_f_NL != 0 runs on one rank (the forward z transform of the phi field needs every plane)\n");
-        return 1;
-    }
-    cplx *d_phik = nullptr;
-    if (make_phik(p, pk, &d_phik)) return 1;
-    if (plan_create_ex(p, pk, eig, eig_ppd, 0, 1, 0, d_phik, out)) {
-        hipFree(d_phik);
-        return 1;
-    }
-    (*out)->d_phik_owned = d_phik;
+    if (plan_create_ex(p, pk, eig, eig_ppd, rank, nranks, 0, d_phik, pl)) return 1;
+    pl->d_phik_owned = std::move(d_phik);
+    *out             = pl.release();
     return 0;
 }
 
@@ -914,7 +854,7 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
     const zd_params *p = &pl->p;
     zd::GenConst &g = pl->g;
     if (!pk->is_powerlaw) {
-        HIPCHECK(hipMalloc((void **) &pl->d_pk, sizeof(double) * 3 * (size_t) pk->n));
+        HIPCHECK(pl->d_pk.alloc(3 * (size_t) pk->n));
         HIPCHECK(hipMemcpy(pl->d_pk, pk->x, sizeof(double) * pk->n, hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(pl->d_pk + pk->n, pk->y, sizeof(double) * pk->n, hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(pl->d_pk + 2 * pk->n, pk->y2, sizeof(double) * pk->n, hipMemcpyHostToDevice));
@@ -931,16 +871,14 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
             while (klo < pk->n - 2 && pk->x[klo + 1] <= cell_start) klo++;
             lut[c2] = klo;
         }
-        HIPCHECK(hipMalloc((void **) &pl->d_lut, sizeof(int) * lut.size()));
-        HIPCHECK(hipMemcpy(pl->d_lut, lut.data(), sizeof(int) * lut.size(), hipMemcpyHostToDevice));
+        HIPCHECK(upload(pl->d_lut, lut));
         g.pk_lut     = pl->d_lut;
         g.lut_x0     = x0;
         g.lut_inv_dx = 1.0 / dx;
     }
     if (p->qPLT) {
-        const size_t nb = sizeof(double) * (size_t) eig_ppd * eig_ppd * (eig_ppd / 2 + 1) * 4;
-        HIPCHECK(hipMalloc((void **) &pl->d_eig, nb));
-        HIPCHECK(hipMemcpy(pl->d_eig, eig, nb, hipMemcpyHostToDevice));
+        const size_t n = (size_t) eig_ppd * eig_ppd * (eig_ppd / 2 + 1) * 4;
+        HIPCHECK(upload(pl->d_eig, eig, n));
         g.eig = pl->d_eig;
     }
     // per-plane stream heads == v2rng[] of the reference (power_spectrum.cpp:26-37)
@@ -949,8 +887,7 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
         const zdpcg::Affine plane = zdpcg::jump_map((u128) 2 * ZD_MAX_PPD * ZD_MAX_PPD);
         rows[0] = zdpcg::seed_state((uint64_t) p->seed);
         for (int i = 1; i < pl->half; i++) rows[i] = zdpcg::apply(plane, rows[i - 1]);
-        HIPCHECK(hipMalloc((void **) &pl->d_rowstate, sizeof(u128) * rows.size()));
-        HIPCHECK(hipMemcpy(pl->d_rowstate, rows.data(), sizeof(u128) * rows.size(), hipMemcpyHostToDevice));
+        HIPCHECK(upload(pl->d_rowstate, rows));
         g.row_state = pl->d_rowstate;
         // (built once; ZD_NumGPU creates its plans from several host threads at a time)
         static const zdpcg::BitTable bt = [] {
@@ -985,13 +922,10 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
         pl->J.mback_full[1] = row_jump_full(mb > 0 ? mb + wrap : mb - wrap);
     }
     {
-        std::vector<cplx> twN = make_twiddles(pl->N), twL = make_twiddles(pl->L);
-        HIPCHECK(hipMalloc((void **) &pl->d_twN, sizeof(cplx) * twN.size()));
-        HIPCHECK(hipMemcpy(pl->d_twN, twN.data(), sizeof(cplx) * twN.size(), hipMemcpyHostToDevice));
-        HIPCHECK(hipMalloc((void **) &pl->d_twL, sizeof(cplx) * twL.size()));
-        HIPCHECK(hipMemcpy(pl->d_twL, twL.data(), sizeof(cplx) * twL.size(), hipMemcpyHostToDevice));
+        HIPCHECK(upload(pl->d_twN, make_twiddles(pl->N)));
+        HIPCHECK(upload(pl->d_twL, make_twiddles(pl->L)));
         if (!is_pow2(pl->N) && !pl->any) {  // composite transforms (zd_fft_q.h): exp(2 pi i k / P) | exp(2 pi i k / len) | exp(2 pi i k / Q) per length
-            if (upload_twq(pl->N, &pl->d_twq_n) || upload_twq(pl->L, &pl->d_twq_l)) {
+            if (upload_twq(pl->N, pl->d_twq_n) || upload_twq(pl->L, pl->d_twq_l)) {
                 fprintf(stderr, "zeldovich_hip: composite twiddle tables failed\n");
                 return 1;
             }
@@ -1001,8 +935,7 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
         const int nseg = pk->is_powerlaw ? 0 : pk->n - 1;
         if (nseg <= 512 && !tune_env("ZD_GEN_GENERAL")) {
             std::vector<double> T = build_genf_table(pk, nseg, &g.glut_x0, &g.glut_inv_dx);
-            HIPCHECK(hipMalloc((void **) &pl->d_genf, sizeof(double) * T.size()));
-            HIPCHECK(hipMemcpy(pl->d_genf, T.data(), sizeof(double) * T.size(), hipMemcpyHostToDevice));
+            HIPCHECK(upload(pl->d_genf, T));
             g.genf_tab  = pl->d_genf;
             g.genf_n    = (int) T.size();
             g.genf_nseg = nseg;
@@ -1014,12 +947,10 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
         double nmax = p->corner_modes ? 3.0 * half2 : std::min(3.0 * half2, g.k2_cutoff / g.fundamental2 * (1 + 1e-9) + 2);
         const long long n = (long long) nmax + 2;
         if (n <= ((long long) 1 << 26)) {
-            HIPCHECK(hipMalloc((void **) &pl->d_pktab, sizeof(double) * 2 * (size_t) n));
-            if (zd::launch_pk_table(g, (int) n, pl->d_pktab, 0)) {
-                return 1;
-            }
+            HIPCHECK(pl->d_pktab.alloc(2 * (size_t) n));
+            if (zd::launch_pk_table(g, (int) n, pl->d_pktab, 0)) return 1;
             HIPCHECK(hipDeviceSynchronize());
-            g.pk_tab = (const double2 *) pl->d_pktab;
+            g.pk_tab = (const double2 *) pl->d_pktab.get();
         }
     }
     if (g.gen_phi || g.phik) {  // M(k) = 2 g c^2 T(k) k^2 / (3 Omega_M H0^2), zeldovich.cpp:377-383
@@ -1030,16 +961,14 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
         // Normalize(): primordial_norm = power(kmin) / primordial_power(kmin) with norm 1 (power_spectrum.cpp:221-222)
         g.primordial_norm = zd_pk_power(pk, pk->kmin) / (1. * exp(log(pk->kmin) * p->n_s));
         const long long n = 3LL * pl->half * pl->half + 2;
-        HIPCHECK(hipMalloc((void **) &pl->d_fnlM, sizeof(double) * (size_t) n));
-        if (zd::launch_fnl_table(g, (int) n, pl->d_fnlM, 0)) {
-            return 1;
-        }
+        HIPCHECK(pl->d_fnlM.alloc((size_t) n));
+        if (zd::launch_fnl_table(g, (int) n, pl->d_fnlM, 0)) return 1;
         HIPCHECK(hipDeviceSynchronize());
         g.fnl_M = pl->d_fnlM;
     }
-    HIPCHECK(hipMalloc((void **) &pl->d_red, sizeof(zd::Reduce)));
+    HIPCHECK(pl->d_red.alloc(1));
     HIPCHECK(hipMemset(pl->d_red, 0, sizeof(zd::Reduce)));
-    g.var_slots = pl->d_red->sumsq;
+    g.var_slots = pl->d_red.get()->sumsq;
     return 0;
 }
 
@@ -1213,10 +1142,7 @@ static int plan_block_layout(zd_plan *pl, bool v1) {
         }
         std::stable_sort(items.begin(), items.end(), [](const zd::FzItem &a, const zd::FzItem &b) { return a.n > b.n; });
         pl->n_fzitems = (unsigned) items.size();
-        if (!items.empty()) {
-            HIPCHECK(hipMalloc((void **) &pl->d_fzitems, sizeof(zd::FzItem) * items.size()));
-            HIPCHECK(hipMemcpy(pl->d_fzitems, items.data(), sizeof(zd::FzItem) * items.size(), hipMemcpyHostToDevice));
-        }
+        if (!items.empty()) HIPCHECK(upload(pl->d_fzitems, items));
         int dev = 0;
         hipGetDevice(&dev);
         hipDeviceGetAttribute(&pl->ncu, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1231,7 +1157,7 @@ static int plan_block_layout(zd_plan *pl, bool v1) {
 static int plan_stores(zd_plan *pl, bool twr) {
     if (pl->any) {
         if (twr) {
-            if (upload_twq(pl->N, &pl->d_twr_n) || upload_twq(pl->L, &pl->d_twr_l)) {
+            if (upload_twq(pl->N, pl->d_twr_n) || upload_twq(pl->L, pl->d_twr_l)) {
                 fprintf(stderr, "zeldovich_hip: composite twiddle tables failed\n");
                 return 1;
             }
@@ -1252,8 +1178,7 @@ static int plan_stores(zd_plan *pl, bool twr) {
     zd::StoreLayout &S = pl->S;
     std::vector<zd::FieldRow> rows;
     const int64_t fe = field_rows(&pl->p, pl->nranks, &rows);
-    HIPCHECK(hipMalloc((void **) &pl->d_fieldrows, sizeof(zd::FieldRow) * rows.size()));
-    HIPCHECK(hipMemcpy(pl->d_fieldrows, rows.data(), sizeof(zd::FieldRow) * rows.size(), hipMemcpyHostToDevice));
+    HIPCHECK(upload(pl->d_fieldrows, rows));
     pl->F.lG          = S.lG;
     pl->F.lZq         = 0;
     while ((1 << pl->F.lZq) < pl->Zq) pl->F.lZq++;
@@ -1285,9 +1210,9 @@ static int plan_stores(zd_plan *pl, bool twr) {
     Q.zb_rows    = 3 * pl->N;
     Q.kb_rows    = Q.zb_rows * pl->ring_planes;
     Q.chunk_rows = Q.kb_rows;
-    HIPCHECK(zd_store_alloc((void **) &pl->d_ring, (size_t) Q.chunk_rows * Q.pitch * 16));
+    HIPCHECK(pl->d_ring.store_alloc((size_t) Q.chunk_rows * Q.pitch));
     if (pl->dens)  // the density array delta_r0 + i delta_r1 of the ring's planes: [plane][y][x]
-        HIPCHECK(zd_store_alloc((void **) &pl->d_ring_dens, (size_t) pl->ring_planes * pl->N * Q.pitch * 16));
+        HIPCHECK(pl->d_ring_dens.store_alloc((size_t) pl->ring_planes * pl->N * Q.pitch));
     return 0;
 }
 
@@ -1320,18 +1245,18 @@ static int plan_slabs(zd_plan *pl, bool v1, int64_t eig_ppd) {
     // done once per column of a slab (k_eig_lines) instead of once per mode; one slab of lines, refilled on the generator's
     // stream in front of every generator launch
     if (g.qPLT && g.genf_tab && !v1 && eig_ppd % N != 0) {
-        const size_t nb = (size_t) (eig_ppd / 2 + 1) * rows * N * 4 * sizeof(double);
-        if (nb <= ((size_t) 1 << 30)) {
-            HIPCHECK(hipMalloc((void **) &pl->d_eiglines, nb));
+        const size_t n = (size_t) (eig_ppd / 2 + 1) * rows * N * 4;
+        if (n * sizeof(double) <= ((size_t) 1 << 30)) {
+            HIPCHECK(pl->d_eiglines.alloc(n));
             g.eig_lines = pl->d_eiglines;
             g.eig_rows  = rows;
         }
     }
     if (v1) {
         pl->v1_block = (int) (N / p->numblock);
-        HIPCHECK(hipMalloc((void **) &pl->d_v1streams, sizeof(zd::V1Stream) * (size_t) pl->v1_block));
-        HIPCHECK(hipMalloc((void **) &pl->d_v1dev, (size_t) rows * N * N * sizeof(double2)));
-        HIPCHECK(hipMalloc((void **) &pl->d_v1err, sizeof(int)));
+        HIPCHECK(pl->d_v1streams.alloc((size_t) pl->v1_block));
+        HIPCHECK(pl->d_v1dev.alloc((size_t) rows * N * N));
+        HIPCHECK(pl->d_v1err.alloc(1));
         HIPCHECK(hipMemset(pl->d_v1err, 0, sizeof(int)));
         g.v1dev = pl->d_v1dev;
     }
@@ -1349,7 +1274,7 @@ static int plan_slabs(zd_plan *pl, bool v1, int64_t eig_ppd) {
 #endif
         pl->gen_max_wgs = std::max(1, per_cu) * std::max(1, ncu);
         pl->n_tilectr   = 2 * (pl->Hq / rows) + 2;  // per pass parity: the next pass's generator may already run
-        HIPCHECK(hipMalloc((void **) &pl->d_tilectr, sizeof(unsigned) * pl->n_tilectr));
+        HIPCHECK(pl->d_tilectr.alloc((size_t) pl->n_tilectr));
     }
     // ring size: 1 slab without the overlap, else 2 + what the store (allocated by the caller afterwards) leaves
     int K = 1;
@@ -1368,8 +1293,8 @@ static int plan_slabs(zd_plan *pl, bool v1, int64_t eig_ppd) {
         }
         if (const char *env = tune_env("ZD_Y_SLABS")) K = std::max(2, atoi(env));
     }
-    pl->d_Y.assign(K, nullptr);
-    for (int i = 0; i < K; i++) HIPCHECK(hipMalloc((void **) &pl->d_Y[i], (size_t) row_b * rows));
+    pl->d_Y.resize(K);
+    for (int i = 0; i < K; i++) HIPCHECK(pl->d_Y[i].alloc((size_t) row_b * rows / sizeof(cplx)));
     if (pl->overlap) {
 #ifdef ZD_TUNING
         // A/B (VERDICT r4 #5 i): ZD_CU_SPLIT = n gives the z FFT's stream n CUs of every XCD's 32 and the generator's stream
@@ -1378,29 +1303,33 @@ static int plan_slabs(zd_plan *pl, bool v1, int64_t eig_ppd) {
             const int nf = std::max(1, std::min(31, atoi(env)));
             uint32_t mg[8] = {0}, mf[8] = {0};
             for (int c = 0; c < 256; c++) ((c / 8) < nf ? mf : mg)[c / 32] |= 1u << (c % 32);
-            HIPCHECK(hipExtStreamCreateWithCUMask(&pl->s_gen, 8, mg));
-            HIPCHECK(hipExtStreamCreateWithCUMask(&pl->s_fft, 8, mf));
+            hipStream_t sg = nullptr, sf = nullptr;
+            HIPCHECK(hipExtStreamCreateWithCUMask(&sg, 8, mg));
+            pl->s_gen.reset(sg);
+            HIPCHECK(hipExtStreamCreateWithCUMask(&sf, 8, mf));
+            pl->s_fft.reset(sf);
         } else
 #endif
         {
-            HIPCHECK(hipStreamCreateWithFlags(&pl->s_gen, hipStreamNonBlocking));
-            HIPCHECK(hipStreamCreateWithFlags(&pl->s_fft, hipStreamNonBlocking));
+            HIPCHECK(pl->s_gen.create());
+            HIPCHECK(pl->s_fft.create());
         }
-        HIPCHECK(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
-        pl->ev_gen.assign(K, nullptr);
-        pl->ev_fft.assign(K, nullptr);
+        HIPCHECK(pl->ev_fork.create(hipEventDisableTiming));
+        pl->ev_gen.resize(K);
+        pl->ev_fft.resize(K);
         for (int i = 0; i < K; i++) {
-            HIPCHECK(hipEventCreateWithFlags(&pl->ev_gen[i], hipEventDisableTiming));
-            HIPCHECK(hipEventCreateWithFlags(&pl->ev_fft[i], hipEventDisableTiming));
+            HIPCHECK(pl->ev_gen[i].create(hipEventDisableTiming));
+            HIPCHECK(pl->ev_fft[i].create(hipEventDisableTiming));
         }
     }
     return 0;
 }
 
-// a plan of the shape an accepted route gives; each part above fills its own members; a plan that fails half-way is destroyed here, once
+// a plan of the shape an accepted route gives; each part above fills its own members; a plan that fails half-way releases what it has
 static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
-                           int role, const cplx *phik, zd_plan **out) {
-    zd_plan *pl   = new zd_plan;
+                           int role, const cplx *phik, PlanPtr &out) {
+    PlanPtr plan(new zd_plan);
+    zd_plan *pl   = plan.get();
     pl->p         = *p;
     pl->rank      = rank;
     pl->nranks    = nranks;
@@ -1468,16 +1397,13 @@ static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk,
     }
     if (role == zd::ROLE_PHI) g.qPLT = 0;  // the phi pass stops before the displacement algebra (zeldovich.cpp:385-391)
     plan_zstage_jobs(pl);
-    if (plan_device_tables(pl, pk, eig, eig_ppd) || plan_block_layout(pl, v1) || plan_stores(pl, rt.twr) || plan_slabs(pl, v1, eig_ppd)) {
-        zd_plan_destroy(pl);
-        return 1;
-    }
-    *out = pl;
+    if (plan_device_tables(pl, pk, eig, eig_ppd) || plan_block_layout(pl, v1) || plan_stores(pl, rt.twr) || plan_slabs(pl, v1, eig_ppd)) return 1;
+    out = std::move(plan);
     return 0;
 }
 
 static int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
-                          int phi_mode, const cplx *phik, zd_plan **out) {
+                          int phi_mode, const cplx *phik, PlanPtr &out) {
     const zd_params pc = zd::canonical(p_in);
     const int role = phi_mode == 1 ? zd::ROLE_PHI : phi_mode == 2 ? zd::ROLE_LPT2_GRAD : (phik && !pc.q2LPT) ? zd::ROLE_PHIK : zd::ROLE_MAIN;
     if (pc.q2LPT && role == zd::ROLE_MAIN && !phik) {  // (zd_plan_create and zd_generate run the second-order round first)
@@ -1489,19 +1415,17 @@ static int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *
     Route ra, rb;
     if (role == zd::ROLE_MAIN && zd::plt_dens_split(&pc, nranks) && have_eig && split_routes(&pc, pc.stream_factor, &pa, &pb, &ra, &rb) && ra.ok()
         && rb.ok()) {
-        zd_plan *A = nullptr, *B = nullptr;
-        bool ok = plan_create_one(&pa, ra, pk, eig, eig_ppd, rank, nranks, role, nullptr, &A) == 0
-                  && plan_create_one(&pb, rb, pk, nullptr, 0, rank, nranks, role, nullptr, &B) == 0;
-        if (ok) ok = zd_store_alloc((void **) &A->d_dens_pass, (size_t) A->Zq * pc.ppd * pc.ppd * sizeof(float)) == hipSuccess;
-        if (ok) {
-            A->dens_sub     = B;
+        PlanPtr A, B;
+        if (plan_create_one(&pa, ra, pk, eig, eig_ppd, rank, nranks, role, nullptr, A) == 0
+            && plan_create_one(&pb, rb, pk, nullptr, 0, rank, nranks, role, nullptr, B) == 0
+            && A->d_dens_pass.store_alloc((size_t) A->Zq * pc.ppd * pc.ppd) == hipSuccess) {
             A->p            = pc;  // (what the callers read back: ZD_qdensity = 1)
             A->store_bytes_ = std::max(A->store_bytes_, B->store_bytes_);
-            *out            = A;
+            A->dens_sub     = std::move(B);
+            out             = std::move(A);
             return 0;
         }
-        zd_plan_destroy(B);
-        zd_plan_destroy(A);  // the run falls back to the reference arrays (convolution path)
+        // (A and B go away here) the run falls back to the reference arrays (convolution path)
     }
     const Route rt = route(&pc, pc.stream_factor, nranks, role, rank, have_eig);
     if (!rt.ok()) {
@@ -1511,48 +1435,11 @@ static int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *
     return plan_create_one(&pc, rt, pk, eig, eig_ppd, rank, nranks, role, phik, out);
 }
 
-void zd_plan_destroy(zd_plan *pl) {
-    if (!pl) return;
-    collect_events(pl);
-    hipFree(pl->d_fzitems);
-    hipFree(pl->d_pk);
-    hipFree(pl->d_lut);
-    hipFree(pl->d_pktab);
-    hipFree(pl->d_fnlM);
-    hipFree(pl->d_eig);
-    hipFree(pl->d_eiglines);
-    hipFree(pl->d_rowstate);
-    hipFree(pl->d_twN);
-    hipFree(pl->d_twL);
-    hipFree(pl->d_twq_n);
-    hipFree(pl->d_twq_l);
-    hipFree(pl->d_genf);
-    hipFree(pl->d_tilectr);
-    hipFree(pl->d_red);
-    hipFree(pl->d_fieldrows);
-    hipFree(pl->d_ring);
-    hipFree(pl->d_ring_dens);
-    hipFree(pl->d_dens_pass);
-    zd_plan_destroy(pl->dens_sub);
-    hipFree(pl->d_v1streams);
-    hipFree(pl->d_v1dev);
-    hipFree(pl->d_v1err);
-    hipFree(pl->d_phik_owned);
-    for (cplx *b : pl->d_any) hipFree(b);
-    hipFree(pl->d_twr_n);
-    hipFree(pl->d_twr_l);
-    for (cplx *y : pl->d_Y) hipFree(y);
-    if (pl->s_gen) hipStreamDestroy(pl->s_gen);
-    if (pl->s_fft) hipStreamDestroy(pl->s_fft);
-    if (pl->ev_fork) hipEventDestroy(pl->ev_fork);
-    for (hipEvent_t e : pl->ev_pipe)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : pl->ev_gen)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : pl->ev_fft)
-        if (e) hipEventDestroy(e);
-    delete pl;
+zd_plan::~zd_plan() {  // the members release themselves afterwards
+    collect_events(this);
+    zdown::live(-1);
 }
+void zd_plan_destroy(zd_plan *pl) { delete pl; }
 
 int32_t zd_plan_narray(const zd_plan *pl) { return pl->narray; }
 int32_t zd_plan_store_mode(const zd_plan *pl) {
@@ -1659,17 +1546,16 @@ static int stage_z_impl(zd_plan *pl, int residue, void *d_send, hipStream_t st, 
         // PLT + ZD_qdensity = 1 on a composite grid (plan_create_ex): first the whole density-only pass — Z stage into this store,
         // y / x stages of its density array — whose planes are the planes of this pass; then the PLT pass proper over the same
         // store.  All in stream order on st (a detached call included: the density planes are kept in ONE buffer).
-        zd_plan *B = pl->dens_sub;
+        zd_plan *B = pl->dens_sub.get();
         if (detached && wait_ev) HIPCHECK(hipStreamWaitEvent(st, wait_ev, 0));
         B->pass_step = pl->pass_step;
         if (stage_z_impl(B, residue, d_send, st, false, nullptr, nullptr)) return 1;
         pl->dens_pass = -1;
         if (zd_plan_stage_x_group(B, residue, d_send, B->Zq, 0, 0, (int64_t) B->Zq * 2, nullptr, pl->d_dens_pass, st)) return 1;
         pl->dens_pass = residue;
-        zd_plan *sub = pl->dens_sub;
-        pl->dens_sub = nullptr;  // (the PLT pass itself)
+        PlanPtr sub = std::move(pl->dens_sub);  // (the PLT pass itself)
         const int rc = stage_z_impl(pl, residue, d_send, st, false, nullptr, nullptr);
-        pl->dens_sub = sub;
+        pl->dens_sub = std::move(sub);
         if (rc) return rc;
         if (detached && done_ev) HIPCHECK(hipEventRecord(done_ev, st));
         return 0;
@@ -1951,7 +1837,7 @@ int zd_plan_stats(zd_plan *pl, zd_stats *out) {
     }
     if (pl->dens_sub) {  // the density-only half of a PLT + ZD_qdensity = 1 run: its kernels belong to this run's time
         zd_stats sb;
-        if (zd_plan_stats(pl->dens_sub, &sb)) return 1;
+        if (zd_plan_stats(pl->dens_sub.get(), &sb)) return 1;
         for (int k = 0; k < ZD_K_COUNT; k++) {
             out->kernel_ms[k] += sb.kernel_ms[k];
             out->kernel_launches[k] += sb.kernel_launches[k];
@@ -2003,27 +1889,23 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
         p.stream_factor = R;
     }
     // ---- f_NL: phi field -> local transform -> Fourier space again (zeldovich.cpp:945-960) ----
-    cplx *d_phik = nullptr;
+    DevBuf<cplx> d_phik;  // PhiK or S(k), until the plan exists and owns it
     if (p.f_NL != 0.) {
-        if (make_phik(&p, pk, &d_phik)) return 1;
+        if (make_phik(&p, pk, d_phik)) return 1;
         HIPCHECK(hipMemGetInfo(&free_b, &total_b));
         if (p_in->stream_factor <= 0) {
             // (PhiK is allocated by now: it is part of what the chooser counts)
             const int R2 = zd_choose_stream_factor(&p, 1, (int64_t) free_b - ((int64_t) 16 << 30) + fnl_phik_bytes(N));
-            if (R2 < 0) {
-                hipFree(d_phik);
-                return 1;
-            }
+            if (R2 < 0) return 1;
             p.stream_factor = R2;
         }
     }
     // ---- ZD_q2LPT: the second-order round (zd_kernels_lpt2.hip); the chooser has counted S(k) beside the passes' stores ----
-    if (p.q2LPT && make_lpt2_source(&p, pk, &d_phik)) return 1;
-    zd_plan *pl = nullptr;
-    if (plan_create_ex(&p, pk, eig, eig_ppd, 0, 1, 0, d_phik, &pl)) {
-        hipFree(d_phik);
-        return 1;
-    }
+    if (p.q2LPT && make_lpt2_source(&p, pk, d_phik)) return 1;
+    PlanPtr plan;
+    if (plan_create_ex(&p, pk, eig, eig_ppd, 0, 1, 0, d_phik, plan)) return 1;
+    zd_plan *pl      = plan.get();
+    pl->d_phik_owned = std::move(d_phik);
     const int R = pl->R, recsize = pl->ec.recsize, npass = pl->npass, pstep = pl->pstep;
     const int64_t Pp = zd_plan_local_planes(pl);  // planes delivered per pass
     const bool want_rec = pl->narray >= 2 && !pl->dens_only, want_dens = p.qdensity != 0;
@@ -2034,13 +1916,12 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
     // chunk i and the callback of chunk i-1 overlap (round 1 serialised the three).  The callback is still invoked
     // from ONE thread, in production order.
     constexpr int NB = 2;
-    void *d_store = nullptr, *d_rec[NB] = {nullptr, nullptr};
-    float *d_dens[NB] = {nullptr, nullptr};
-    char *h_rec[NB] = {nullptr, nullptr};
-    float *h_dens[NB] = {nullptr, nullptr};
-    hipEvent_t ev_x[NB] = {nullptr, nullptr}, ev_c[NB] = {nullptr, nullptr};
-    hipStream_t s_copy = nullptr;
-    int rc = 1;
+    DevBuf<void> d_store, d_rec[NB];
+    DevBuf<float> d_dens[NB];
+    PinnedBuf<char> h_rec[NB];
+    PinnedBuf<float> h_dens[NB];
+    Event ev_x[NB], ev_c[NB];
+    Stream s_copy;
     hipStream_t st = 0;
     // planes handed over per x-stage launch (a multiple of the plane step)
     const int64_t plane_b = N * N * (int64_t) (want_rec ? recsize : 0) + (want_dens ? N * N * 4 : 0);
@@ -2060,150 +1941,150 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
     bool slot_busy[NB] = {false, false}, done = false;
     std::atomic<int> cb_failed{0};
     std::thread writer;
-    std::chrono::steady_clock::time_point t0;
-    do {
-        if (zd_store_alloc(&d_store, (size_t) zd_plan_exchange_bytes(pl)) != hipSuccess) {
-            fprintf(stderr, "zeldovich_hip: cannot allocate the %.2f GB block store\n", zd_plan_exchange_bytes(pl) / 1e9);
+    // However the function is left: the writer is joined and the device idle before anything above — all of which the writer or
+    // queued work may still read — is released
+    struct Quiesce {
+        std::function<void()> f;
+        ~Quiesce() { f(); }
+    } quiesce{[&] {
+        if (writer.joinable()) {
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                done = true;
+                queue.clear();
+            }
+            cv.notify_all();
+            writer.join();
+        }
+        hipDeviceSynchronize();
+    }};
+    if (d_store.store_alloc((size_t) zd_plan_exchange_bytes(pl)) != hipSuccess) {
+        fprintf(stderr, "zeldovich_hip: cannot allocate the %.2f GB block store\n", zd_plan_exchange_bytes(pl) / 1e9);
+        return 1;
+    }
+    for (int b2 = 0; b2 < nbuf; b2++) {
+        if (want_rec && d_rec[b2].alloc((size_t) chunk * N * N * recsize) != hipSuccess) return 1;
+        if (want_dens && d_dens[b2].alloc((size_t) chunk * N * N) != hipSuccess) return 1;
+        if (!cb) continue;
+        if (want_rec && h_rec[b2].alloc((size_t) chunk * N * N * recsize) != hipSuccess) return 1;
+        if (want_dens && h_dens[b2].alloc((size_t) chunk * N * N) != hipSuccess) return 1;
+        if (ev_x[b2].create(hipEventDisableTiming) != hipSuccess || ev_c[b2].create(hipEventDisableTiming) != hipSuccess) return 1;
+    }
+    if (cb && s_copy.create() != hipSuccess) return 1;
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    if (cb) {
+        writer = std::thread([&]() {
+            for (;;) {
+                Item it;
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return done || !queue.empty(); });
+                    if (queue.empty()) return;
+                    it = queue.front();
+                    queue.pop_front();
+                }
+                if (hipEventSynchronize(ev_c[it.slot]) != hipSuccess) cb_failed.store(1);
+                for (int64_t i = 0; i < it.n && !cb_failed.load(); i++) {
+                    if (it.only >= 0 && it.first + i != it.only) continue;
+                    const int64_t z = zd_plan_plane_z(pl, it.pass, it.first + i);
+                    if (cb(user, z, N * N, want_rec ? h_rec[it.slot] + (size_t) i * N * N * recsize : nullptr,
+                           want_dens ? h_dens[it.slot] + (size_t) i * N * N : nullptr))
+                        cb_failed.store(1);
+                }
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    slot_busy[it.slot] = false;
+                }
+                cv.notify_all();
+            }
+        });
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    bool fail = false;
+    // ZD_qoneslab (zeldovich.cpp:669): only that slab is wanted -> only its pass and its store plane are finished
+    int want_pass = -1;
+    int64_t want_plane = -1;
+    if (p.qoneslab >= 0) {
+        const int r = p.qoneslab % R;
+        want_pass   = r % npass;
+        want_plane  = (int64_t) (p.qoneslab / R) * pstep + r / npass;
+    }
+    long long nchunk = 0;
+    for (int r = 0; r < npass && !fail; r++) {
+        if (want_pass >= 0 && r != want_pass) continue;
+        if (zd_plan_stage_z(pl, r, d_store, st) || zd_plan_stage_y(pl, d_store, st)) {
+            fail = true;
             break;
         }
-        bool ok = true;
-        for (int b2 = 0; b2 < nbuf && ok; b2++) {
-            if (want_rec && hipMalloc(&d_rec[b2], (size_t) chunk * N * N * recsize) != hipSuccess) ok = false;
-            if (want_dens && hipMalloc((void **) &d_dens[b2], (size_t) chunk * N * N * 4) != hipSuccess) ok = false;
-            if (cb) {
-                if (want_rec && hipHostMalloc((void **) &h_rec[b2], (size_t) chunk * N * N * recsize) != hipSuccess) ok = false;
-                if (want_dens && hipHostMalloc((void **) &h_dens[b2], (size_t) chunk * N * N * 4) != hipSuccess) ok = false;
-                if (hipEventCreateWithFlags(&ev_x[b2], hipEventDisableTiming) != hipSuccess) ok = false;
-                if (hipEventCreateWithFlags(&ev_c[b2], hipEventDisableTiming) != hipSuccess) ok = false;
+        for (int64_t pl0 = 0; pl0 < Pp && !fail; pl0 += chunk) {
+            int64_t first = pl0, n = std::min<int64_t>(chunk, Pp - pl0);
+            if (want_plane >= 0) {
+                if (want_plane < pl0 || want_plane >= pl0 + n) continue;
+                first = want_plane / pstep * pstep;
+                n     = pstep;
             }
-        }
-        if (!ok) break;
-        if (cb && hipStreamCreateWithFlags(&s_copy, hipStreamNonBlocking) != hipSuccess) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (cb) {
-            writer = std::thread([&]() {
-                for (;;) {
-                    Item it;
-                    {
-                        std::unique_lock<std::mutex> lk(mu);
-                        cv.wait(lk, [&] { return done || !queue.empty(); });
-                        if (queue.empty()) return;
-                        it = queue.front();
-                        queue.pop_front();
-                    }
-                    if (hipEventSynchronize(ev_c[it.slot]) != hipSuccess) cb_failed.store(1);
-                    for (int64_t i = 0; i < it.n && !cb_failed.load(); i++) {
-                        if (it.only >= 0 && it.first + i != it.only) continue;
-                        const int64_t z = zd_plan_plane_z(pl, it.pass, it.first + i);
-                        if (cb(user, z, N * N, want_rec ? h_rec[it.slot] + (size_t) i * N * N * recsize : nullptr,
-                               want_dens ? h_dens[it.slot] + (size_t) i * N * N : nullptr))
-                            cb_failed.store(1);
-                    }
-                    {
-                        std::lock_guard<std::mutex> lk(mu);
-                        slot_busy[it.slot] = false;
-                    }
-                    cv.notify_all();
-                }
-            });
-        }
-        t0 = std::chrono::steady_clock::now();
-        bool fail = false;
-        // ZD_qoneslab (zeldovich.cpp:669): only that slab is wanted -> only its pass and its store plane are finished
-        int want_pass = -1;
-        int64_t want_plane = -1;
-        if (p.qoneslab >= 0) {
-            const int r = p.qoneslab % R;
-            want_pass   = r % npass;
-            want_plane  = (int64_t) (p.qoneslab / R) * pstep + r / npass;
-        }
-        long long nchunk = 0;
-        for (int r = 0; r < npass && !fail; r++) {
-            if (want_pass >= 0 && r != want_pass) continue;
-            if (zd_plan_stage_z(pl, r, d_store, st) || zd_plan_stage_y(pl, d_store, st)) {
-                fail = true;
-                break;
-            }
-            for (int64_t pl0 = 0; pl0 < Pp && !fail; pl0 += chunk) {
-                int64_t first = pl0, n = std::min<int64_t>(chunk, Pp - pl0);
-                if (want_plane >= 0) {
-                    if (want_plane < pl0 || want_plane >= pl0 + n) continue;
-                    first = want_plane / pstep * pstep;
-                    n     = pstep;
-                }
-                const int slot = cb ? (int) (nchunk++ % NB) : 0;
-                if (cb) {  // the writer has finished with this slot's host buffer (chunk i - 2) — and with it its D2H copy
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return !slot_busy[slot] || cb_failed.load(); });
-                    if (cb_failed.load()) {
-                        fail = true;
-                        break;
-                    }
-                    slot_busy[slot] = true;
-                }
-                if (zd_plan_stage_x(pl, r, d_store, first, n, d_rec[slot], d_dens[slot], st)) {
+            const int slot = cb ? (int) (nchunk++ % NB) : 0;
+            if (cb) {  // the writer has finished with this slot's host buffer (chunk i - 2) — and with it its D2H copy
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return !slot_busy[slot] || cb_failed.load(); });
+                if (cb_failed.load()) {
                     fail = true;
                     break;
                 }
-                if (cb) {
-                    if (hipEventRecord(ev_x[slot], st) != hipSuccess || hipStreamWaitEvent(s_copy, ev_x[slot], 0) != hipSuccess) fail = true;
-                    if (want_rec && hipMemcpyAsync(h_rec[slot], d_rec[slot], (size_t) n * N * N * recsize, hipMemcpyDeviceToHost, s_copy) != hipSuccess) fail = true;
-                    if (want_dens && hipMemcpyAsync(h_dens[slot], d_dens[slot], (size_t) n * N * N * 4, hipMemcpyDeviceToHost, s_copy) != hipSuccess) fail = true;
-                    if (hipEventRecord(ev_c[slot], s_copy) != hipSuccess) fail = true;
-                    {
-                        std::lock_guard<std::mutex> lk(mu);
-                        queue.push_back(Item{slot, r, first, n, want_plane});
-                    }
-                    cv.notify_all();
+                slot_busy[slot] = true;
+            }
+            if (zd_plan_stage_x(pl, r, d_store, first, n, d_rec[slot], d_dens[slot], st)) {
+                fail = true;
+                break;
+            }
+            if (cb) {
+                if (hipEventRecord(ev_x[slot], st) != hipSuccess || hipStreamWaitEvent(s_copy, ev_x[slot], 0) != hipSuccess) fail = true;
+                if (want_rec && hipMemcpyAsync(h_rec[slot], d_rec[slot], (size_t) n * N * N * recsize, hipMemcpyDeviceToHost, s_copy) != hipSuccess) fail = true;
+                if (want_dens && hipMemcpyAsync(h_dens[slot], d_dens[slot], (size_t) n * N * N * 4, hipMemcpyDeviceToHost, s_copy) != hipSuccess) fail = true;
+                if (hipEventRecord(ev_c[slot], s_copy) != hipSuccess) fail = true;
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    queue.push_back(Item{slot, r, first, n, want_plane});
                 }
+                cv.notify_all();
             }
         }
-        if (cb) {  // drain
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return (queue.empty() && !slot_busy[0] && !slot_busy[1]) || cb_failed.load(); });
-            }
-            if (cb_failed.load()) fail = true;
-        }
-        if (fail) break;
-        if (zd_plan_stats(pl, out)) break;
-        out->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        rc = 0;
-    } while (0);
-    if (writer.joinable()) {
+    }
+    if (cb) {  // drain
         {
-            std::lock_guard<std::mutex> lk(mu);
-            done = true;
-            queue.clear();
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return (queue.empty() && !slot_busy[0] && !slot_busy[1]) || cb_failed.load(); });
         }
-        cv.notify_all();
-        writer.join();
+        if (cb_failed.load()) fail = true;
     }
-    hipDeviceSynchronize();
-    hipFree(d_phik);
-    hipFree(d_store);
-    for (int b2 = 0; b2 < NB; b2++) {
-        hipFree(d_rec[b2]);
-        hipFree(d_dens[b2]);
-        if (h_rec[b2]) hipHostFree(h_rec[b2]);
-        if (h_dens[b2]) hipHostFree(h_dens[b2]);
-        if (ev_x[b2]) hipEventDestroy(ev_x[b2]);
-        if (ev_c[b2]) hipEventDestroy(ev_c[b2]);
-    }
-    if (s_copy) hipStreamDestroy(s_copy);
-    zd_plan_destroy(pl);
-    return rc;
+    if (fail || zd_plan_stats(pl, out)) return 1;
+    out->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
 }
 
 #ifdef ZD_TESTING
 // ------------------------------------------------------------------------------------------------
 // device test hooks
 
-static int make_test_gen(const zd_params *p, const zd_pk *pk, zd_plan **pl) {
+int64_t zd_test_live_handles(void) { return (int64_t) zdown::g_live.load(); }
+
+// The three generator hooks: a plan of the job, the mode list up, 16 or 24 bytes per mode down.  which 0: the two uint64 draws,
+// 1: Re D, Im D, 2: Re D, Im D, fundamental / |k|^2 through the table arithmetic
+static int test_modes_run(const zd_params *p, const zd_pk *pk, int64_t n, const int32_t *kxyz, int which, void *out) {
     zd_params q = *p;
     q.qPLT      = 0;
     q.stream_factor = q.ppd > 4096 ? (int) (q.ppd / 4096) : 1;  // z-FFT kernels exist up to length 4096
-    return zd_plan_create(&q, pk, nullptr, 0, 0, 1, pl);
+    zd_plan *raw = nullptr;
+    if (zd_plan_create(&q, pk, nullptr, 0, 0, 1, &raw)) return 1;
+    PlanPtr pl(raw);
+    const size_t nb = (which == 2 ? 24 : 16) * (size_t) n;
+    DevBuf<int> d_k;
+    DevBuf<void> d_o;
+    if (upload(d_k, kxyz, 3 * (size_t) n) != hipSuccess || d_o.alloc(nb) != hipSuccess) return 1;
+    if (which == 2 ? zd::launch_test_modes_table(pl->g, n, d_k, (double *) d_o.get(), 0)
+                   : zd::launch_test_modes(pl->g, n, d_k, which == 0 ? (uint64_t *) d_o.get() : nullptr, which == 1 ? (double *) d_o.get() : nullptr, 0))
+        return 1;
+    return hipMemcpy(out, d_o, nb, hipMemcpyDeviceToHost) != hipSuccess;
 }
 
 int zd_test_draws(int64_t seed, int64_t n, const int32_t *kxyz, uint64_t *out) {
@@ -2222,63 +2103,11 @@ int zd_test_draws(int64_t seed, int64_t n, const int32_t *kxyz, uint64_t *out) {
     pk.is_powerlaw = 1;
     pk.powerlaw_index = -1;
     pk.normalization = 1;
-    zd_plan *pl = nullptr;
-    if (make_test_gen(&p, &pk, &pl)) return 1;
-    int *d_k = nullptr;
-    uint64_t *d_o = nullptr;
-    int rc = 1;
-    do {
-        if (hipMalloc((void **) &d_k, sizeof(int) * 3 * n) != hipSuccess) break;
-        if (hipMalloc((void **) &d_o, sizeof(uint64_t) * 2 * n) != hipSuccess) break;
-        if (hipMemcpy(d_k, kxyz, sizeof(int) * 3 * n, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (zd::launch_test_modes(pl->g, n, d_k, d_o, nullptr, 0)) break;
-        if (hipMemcpy(out, d_o, sizeof(uint64_t) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    hipFree(d_k);
-    hipFree(d_o);
-    zd_plan_destroy(pl);
-    return rc;
+    return test_modes_run(&p, &pk, n, kxyz, 0, out);
 }
-
-int zd_test_modes(const zd_params *p, const zd_pk *pk, int64_t n, const int32_t *kxyz, double *D) {
-    zd_plan *pl = nullptr;
-    if (make_test_gen(p, pk, &pl)) return 1;
-    int *d_k = nullptr;
-    double *d_o = nullptr;
-    int rc = 1;
-    do {
-        if (hipMalloc((void **) &d_k, sizeof(int) * 3 * n) != hipSuccess) break;
-        if (hipMalloc((void **) &d_o, sizeof(double) * 2 * n) != hipSuccess) break;
-        if (hipMemcpy(d_k, kxyz, sizeof(int) * 3 * n, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (zd::launch_test_modes(pl->g, n, d_k, nullptr, d_o, 0)) break;
-        if (hipMemcpy(D, d_o, sizeof(double) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    hipFree(d_k);
-    hipFree(d_o);
-    zd_plan_destroy(pl);
-    return rc;
-}
-
+int zd_test_modes(const zd_params *p, const zd_pk *pk, int64_t n, const int32_t *kxyz, double *D) { return test_modes_run(p, pk, n, kxyz, 1, D); }
 int zd_test_modes_table(const zd_params *p, const zd_pk *pk, int64_t n, const int32_t *kxyz, double *out) {
-    zd_plan *pl = nullptr;
-    if (make_test_gen(p, pk, &pl)) return 1;
-    int *d_k = nullptr;
-    double *d_o = nullptr;
-    int rc = 1;
-    do {
-        if (hipMalloc((void **) &d_k, sizeof(int) * 3 * n) != hipSuccess) break;
-        if (hipMalloc((void **) &d_o, sizeof(double) * 3 * n) != hipSuccess) break;
-        if (hipMemcpy(d_k, kxyz, sizeof(int) * 3 * n, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (zd::launch_test_modes_table(pl->g, n, d_k, d_o, 0)) break;
-        if (hipMemcpy(out, d_o, sizeof(double) * 3 * n, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    hipFree(d_k);
-    hipFree(d_o);
-    zd_plan_destroy(pl);
-    return rc;
+    return test_modes_run(p, pk, n, kxyz, 2, out);
 }
 
 int zd_test_generate_loopback(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, zd_slab_cb cb, void *user,
@@ -2288,92 +2117,35 @@ int zd_test_generate_loopback(const zd_params *p, const zd_pk *pk, const double 
 }
 
 int zd_test_v1_words(int64_t seed, int32_t nblocks, uint32_t *out) {
-    zd::V1Stream *d_s = nullptr;
-    uint32_t *d_o = nullptr;
-    int rc = 1;
-    do {
-        if (nblocks <= 0) break;
-        if (hipMalloc((void **) &d_s, sizeof(zd::V1Stream)) != hipSuccess) break;
-        if (hipMalloc((void **) &d_o, sizeof(uint32_t) * 624 * (size_t) nblocks) != hipSuccess) break;
-        if (zd::launch_v1_seed((unsigned long long) seed, 1, d_s, 0)) break;
-        if (zd::launch_test_v1_words(d_s, nblocks, d_o, 0)) break;
-        if (hipMemcpy(out, d_o, sizeof(uint32_t) * 624 * (size_t) nblocks, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    hipFree(d_s);
-    hipFree(d_o);
-    return rc;
+    if (nblocks <= 0) return 1;
+    DevBuf<zd::V1Stream> d_s;
+    DevBuf<uint32_t> d_o;
+    if (d_s.alloc(1) != hipSuccess || d_o.alloc(624 * (size_t) nblocks) != hipSuccess) return 1;
+    if (zd::launch_v1_seed((unsigned long long) seed, 1, d_s, 0) || zd::launch_test_v1_words(d_s, nblocks, d_o, 0)) return 1;
+    return hipMemcpy(out, d_o, sizeof(uint32_t) * 624 * (size_t) nblocks, hipMemcpyDeviceToHost) != hipSuccess;
 }
 
-static int test_fft_composite(int32_t n, int64_t lines, int32_t axis_kind, const double *in, double *out) {
-    int P = 0, Q = 0;
-    const int W = zd::test_fftq_tile_width(n);
-    if (!zd::np2_split(n, &P, &Q) || W == 0 || lines % W) {
-        fprintf(stderr, "zd_test_fft: n=%d is not 2^a * {3, 9, 27, 5, 15, 25, 45, 75, 125, 135, 7, 21, 35, 49}, or lines %% %d != 0\n", n, W);
-        return 1;
-    }
-    std::vector<cplx> twP = make_twiddles(P), twN = make_twiddles(n), twQ = make_twiddles(Q);
-    cplx *d_tw = nullptr, *d_in = nullptr, *d_out = nullptr;
-    const size_t nb = sizeof(cplx) * (size_t) n * lines;
-    int rc = 1;
-    do {
-        if (hipMalloc((void **) &d_tw, sizeof(cplx) * (P + n + Q)) != hipSuccess) break;
-        if (hipMalloc((void **) &d_in, nb) != hipSuccess) break;
-        if (hipMalloc((void **) &d_out, nb) != hipSuccess) break;
-        if (hipMemcpy(d_tw, twP.data(), sizeof(cplx) * P, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d_tw + P, twN.data(), sizeof(cplx) * n, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d_tw + P + n, twQ.data(), sizeof(cplx) * Q, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d_in, in, nb, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (zd::launch_test_fftq(n, axis_kind, d_tw, d_tw + P, d_tw + P + n, d_in, d_out, lines, 0)) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(out, d_out, nb, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    hipFree(d_tw);
-    hipFree(d_in);
-    hipFree(d_out);
-    return rc;
+// one batch of `nel` points through a transform: its twiddles and the input up, launch(tw, in, out) — out == in: in place —, the result down
+static int test_fft_run(const std::vector<cplx> &tw, size_t nel, bool in_place, const double *in, double *out,
+                        const std::function<int(const cplx *, cplx *, cplx *)> &launch) {
+    DevBuf<cplx> d_tw, d_in, d_out;
+    if (tw.empty() || upload(d_tw, tw) != hipSuccess || upload(d_in, (const cplx *) in, nel) != hipSuccess) return 1;
+    if (!in_place && d_out.alloc(nel) != hipSuccess) return 1;
+    cplx *res = in_place ? d_in.get() : d_out.get();
+    if (launch(d_tw, d_in, res) || hipDeviceSynchronize() != hipSuccess) return 1;
+    return hipMemcpy(out, res, sizeof(cplx) * nel, hipMemcpyDeviceToHost) != hipSuccess;
 }
 
 // any length through the convolution kernels (zd_kernels_any.hip); axis_kind as in zd_test_fft
 static int test_fft_any(int32_t n, int64_t lines, int32_t axis_kind, const double *in, double *out) {
+    if (n < 2 || n > 8192) return 1;
     zd::AnyTab tab = {};
-    cplx *bufs[3] = {nullptr, nullptr, nullptr}, *d = nullptr;
-    const size_t nb = sizeof(cplx) * (size_t) n * lines;
-    int rc = 1;
-    do {
-        if (n < 2 || n > 8192) break;
-        if (any_make_tab(n, &tab, bufs)) break;
-        if (hipMalloc((void **) &d, nb) != hipSuccess) break;
-        if (hipMemcpy(d, in, nb, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (axis_kind == 1 ? zd::launch_any_cols(tab, d, 0, lines, (int) lines, 1, -1, 0) : zd::launch_any_lines(tab, d, n, lines, 0)) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(out, d, nb, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    for (cplx *b : bufs) hipFree(b);
-    hipFree(d);
-    return rc;
-}
-
-// the composite transforms of the reference's arrays (zd_kernels_np2_ref.hip), in place, any batch: axis_kind 3 = strided lines
-// (layout [n][lines], k_refq_cols), 4 = contiguous lines ([lines][n], k_refq_lines)
-static int test_fft_refq(int32_t n, int64_t lines, int32_t axis_kind, const double *in, double *out) {
-    cplx *d_tw = nullptr, *d = nullptr;
-    const size_t nb = sizeof(cplx) * (size_t) n * lines;
-    int rc = 1;
-    do {
-        if (!zd::refq_supported_len(n) || lines < 1 || lines > (1 << 20) || upload_twq(n, &d_tw)) break;
-        if (hipMalloc((void **) &d, nb) != hipSuccess) break;
-        if (hipMemcpy(d, in, nb, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (axis_kind == 3 ? zd::launch_refq_cols(n, d_tw, d, 0, lines, (int) lines, 1, -1, 0) : zd::launch_refq_lines(n, d_tw, d, n, lines, 0)) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(out, d, nb, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    hipFree(d_tw);
-    hipFree(d);
-    return rc;
+    DevBuf<cplx> bufs[3], d;
+    const size_t nel = (size_t) n * lines;
+    if (any_make_tab(n, &tab, bufs) || upload(d, (const cplx *) in, nel) != hipSuccess) return 1;
+    if (axis_kind == 1 ? zd::launch_any_cols(tab, d, 0, lines, (int) lines, 1, -1, 0) : zd::launch_any_lines(tab, d, n, lines, 0)) return 1;
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    return hipMemcpy(out, d, sizeof(cplx) * nel, hipMemcpyDeviceToHost) != hipSuccess;
 }
 
 // the y columns of the arrays split over G ranks (k_refq_ycols) on host columns [image][ky][ncols]: the rows go to a chunked store of
@@ -2381,76 +2153,72 @@ static int test_fft_refq(int32_t n, int64_t lines, int32_t axis_kind, const doub
 // read as zero, every output written (the main pass, the phi round's first y transform); 1: every input read, outputs ky < N/2 only
 // (the phi round's second y transform) — the other rows of `out` keep their input
 int zd_test_ycols(int32_t n, int32_t G, int32_t ncols, int32_t nimg, int32_t mode, const double *in, double *out) {
-    cplx *d_tw = nullptr, *d = nullptr;
     const size_t nel = (size_t) nimg * n * ncols;
-    int rc = 1;
-    do {
-        if (!zd::refq_supported_len(n) || G < 1 || (G & (G - 1)) || (n / 2) % G || ncols < 1 || nimg < 1 || nel > ((size_t) 1 << 26)) break;
-        if (upload_twq(n, &d_tw) || hipMalloc((void **) &d, sizeof(cplx) * nel) != hipSuccess) break;
-        zd::AnyChunks C{n, ncols, 1, G, n / (2 * G), nimg, 0};
-        C.chunk = (long long) nimg * 2 * C.Hq * ncols;
-        const cplx *hin = (const cplx *) in;
-        std::vector<cplx> h(nel);
-        auto at = [&](int b, int y) -> size_t {
-            int c = 0, sl = 0;
-            zd::any_chunk_row(C, y, c, sl);
-            return (size_t) (c * C.chunk + ((long long) b * 2 * C.Hq + sl) * ncols);
-        };
-        for (int b = 0; b < nimg; b++)
-            for (int y = 0; y < n; y++) std::copy(hin + ((size_t) b * n + y) * ncols, hin + ((size_t) b * n + y + 1) * ncols, h.begin() + at(b, y));
-        if (hipMemcpy(d, h.data(), sizeof(cplx) * nel, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (zd::launch_refq_ycols(n, d_tw, C, d, ncols, nimg, mode == 0 ? n / 2 : -1, mode == 0 ? n : n / 2, 0)) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(h.data(), d, sizeof(cplx) * nel, hipMemcpyDeviceToHost) != hipSuccess) break;
-        cplx *hout = (cplx *) out;
-        for (int b = 0; b < nimg; b++)
-            for (int y = 0; y < n; y++) std::copy(h.begin() + at(b, y), h.begin() + at(b, y) + ncols, hout + ((size_t) b * n + y) * ncols);
-        rc = 0;
-    } while (0);
-    hipFree(d_tw);
-    hipFree(d);
-    return rc;
+    if (!zd::refq_supported_len(n) || G < 1 || (G & (G - 1)) || (n / 2) % G || ncols < 1 || nimg < 1 || nel > ((size_t) 1 << 26)) return 1;
+    zd::AnyChunks C{n, ncols, 1, G, n / (2 * G), nimg, 0};
+    C.chunk = (long long) nimg * 2 * C.Hq * ncols;
+    const cplx *hin = (const cplx *) in;
+    std::vector<cplx> h(nel);
+    auto at = [&](int b, int y) -> size_t {
+        int c = 0, sl = 0;
+        zd::any_chunk_row(C, y, c, sl);
+        return (size_t) (c * C.chunk + ((long long) b * 2 * C.Hq + sl) * ncols);
+    };
+    for (int b = 0; b < nimg; b++)
+        for (int y = 0; y < n; y++) std::copy(hin + ((size_t) b * n + y) * ncols, hin + ((size_t) b * n + y + 1) * ncols, h.begin() + at(b, y));
+    DevBuf<cplx> d_tw, d;
+    if (upload_twq(n, d_tw) || upload(d, h) != hipSuccess) return 1;
+    if (zd::launch_refq_ycols(n, d_tw, C, d, ncols, nimg, mode == 0 ? n / 2 : -1, mode == 0 ? n : n / 2, 0)) return 1;
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    if (hipMemcpy(h.data(), d, sizeof(cplx) * nel, hipMemcpyDeviceToHost) != hipSuccess) return 1;
+    cplx *hout = (cplx *) out;
+    for (int b = 0; b < nimg; b++)
+        for (int y = 0; y < n; y++) std::copy(h.begin() + at(b, y), h.begin() + at(b, y) + ncols, hout + ((size_t) b * n + y) * ncols);
+    return 0;
 }
 
 int zd_test_fft(int32_t n, int64_t lines, int32_t axis_kind, const double *in, double *out) {
-    if (axis_kind == 3 || axis_kind == 4) return test_fft_refq(n, lines, axis_kind, in, out);
+    const size_t nel = (size_t) n * lines;
+    // the composite transforms of the reference's arrays (zd_kernels_np2_ref.hip), in place, any batch: axis_kind 3 = strided lines
+    // (layout [n][lines], k_refq_cols), 4 = contiguous lines ([lines][n], k_refq_lines)
+    if (axis_kind == 3 || axis_kind == 4) {
+        if (!zd::refq_supported_len(n) || lines < 1 || lines > (1 << 20)) return 1;
+        return test_fft_run(make_twq(n), nel, true, in, out, [&](const cplx *tw, cplx *d, cplx *) {
+            return axis_kind == 3 ? zd::launch_refq_cols(n, tw, d, 0, lines, (int) lines, 1, -1, 0) : zd::launch_refq_lines(n, tw, d, n, lines, 0);
+        });
+    }
     if (!is_pow2(n)) {
         int P = 0, Q = 0;
         // composite-length kernels where they exist and the batch is whole tiles; else the convolution kernels (any length,
         // ragged batches)
-        if (zd::np2_split(n, &P, &Q) && zd::test_fftq_tile_width(n) > 0 && P >= 8 && lines % zd::test_fftq_tile_width(n) == 0)
-            return test_fft_composite(n, lines, axis_kind, in, out);
-        return test_fft_any(n, lines, axis_kind, in, out);
+        if (!(zd::np2_split(n, &P, &Q) && zd::test_fftq_tile_width(n) > 0 && P >= 8 && lines % zd::test_fftq_tile_width(n) == 0))
+            return test_fft_any(n, lines, axis_kind, in, out);
+        return test_fft_run(make_twq(n), nel, false, in, out, [&](const cplx *tw, cplx *i, cplx *o) {
+            return zd::launch_test_fftq(n, axis_kind, tw, tw + P, tw + P + n, i, o, lines, 0);
+        });
     }
     const int W = zd::test_fft_tile_width(n);
     if (W == 0 || lines % W) {
         fprintf(stderr, "zd_test_fft: n=%d needs lines %% %d == 0\n", n, W);
         return 1;
     }
-    std::vector<cplx> tw = make_twiddles(n);
-    cplx *d_tw = nullptr, *d_in = nullptr, *d_out = nullptr;
-    const size_t nb = sizeof(cplx) * (size_t) n * lines;
-    int rc = 1;
-    do {
-        if (hipMalloc((void **) &d_tw, sizeof(cplx) * n) != hipSuccess) break;
-        if (hipMalloc((void **) &d_in, nb) != hipSuccess) break;
-        if (hipMalloc((void **) &d_out, nb) != hipSuccess) break;
-        if (hipMemcpy(d_tw, tw.data(), sizeof(cplx) * n, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d_in, in, nb, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (zd::launch_test_fft(n, axis_kind, d_tw, d_in, d_out, lines, 0)) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(out, d_out, nb, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    hipFree(d_tw);
-    hipFree(d_in);
-    hipFree(d_out);
-    return rc;
+    return test_fft_run(make_twiddles(n), nel, false, in, out,
+                        [&](const cplx *tw, cplx *i, cplx *o) { return zd::launch_test_fft(n, axis_kind, tw, i, o, lines, 0); });
 }
 
 #endif  // ZD_TESTING
 
 #ifdef ZD_TUNING
+// `reps` launches between two events on the null stream -> milliseconds in all; launch() has run once before
+static int time_launches(int reps, const std::function<int()> &launch, float *ms) {
+    Event e0, e1;
+    if (e0.create() != hipSuccess || e1.create() != hipSuccess || launch() || hipEventRecord(e0, 0) != hipSuccess) return 1;
+    for (int i = 0; i < reps; i++)
+        if (launch()) return 1;
+    if (hipEventRecord(e1, 0) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) return 1;
+    return hipEventElapsedTime(ms, e0, e1) != hipSuccess;
+}
+
 // tuning harness (not part of the product path): time y-pass tile variants on a synthetic store
 int zd_test_yfft_variant(int32_t n, int32_t variant, int32_t narray, int32_t nplanes, int32_t tiled, int32_t reps,
                          double *ms_per_launch) {
@@ -2474,56 +2242,22 @@ int zd_test_yfft_variant(int32_t n, int32_t variant, int32_t narray, int32_t npl
     S.zb_rows = S.a_rows * narray;
     S.kb_rows = S.zb_rows * (nplanes >> lBz);
     S.chunk_rows = S.kb_rows * (n >> lBk);
-    std::vector<cplx> tw = make_twiddles(n);
-    cplx *d_tw = nullptr, *d = nullptr;
-    const size_t nb = (size_t) S.chunk_rows * S.pitch * 16;
-    int rc = 1;
-    do {
-        if (hipMalloc((void **) &d_tw, sizeof(cplx) * n) != hipSuccess) break;
-        if (hipMalloc((void **) &d, nb) != hipSuccess) break;
-        hipMemcpy(d_tw, tw.data(), sizeof(cplx) * n, hipMemcpyHostToDevice);
-        hipMemset(d, 0, nb);
-        if (zd::launch_yfft_variant(variant, S, nplanes, d_tw, d, 0)) break;
-        hipEvent_t e0, e1;
-        hipEventCreate(&e0); hipEventCreate(&e1);
-        hipEventRecord(e0, 0);
-        for (int i = 0; i < reps; i++) zd::launch_yfft_variant(variant, S, nplanes, d_tw, d, 0);
-        hipEventRecord(e1, 0);
-        if (hipEventSynchronize(e1) != hipSuccess) break;
-        float ms = 0;
-        hipEventElapsedTime(&ms, e0, e1);
-        *ms_per_launch = ms / reps;
-        hipEventDestroy(e0); hipEventDestroy(e1);
-        rc = 0;
-    } while (0);
-    hipFree(d_tw); hipFree(d);
-    return rc;
+    const size_t nel = (size_t) S.chunk_rows * S.pitch;
+    DevBuf<cplx> d_tw, d;
+    if (upload(d_tw, make_twiddles(n)) != hipSuccess || d.alloc(nel) != hipSuccess || hipMemset(d, 0, nel * sizeof(cplx)) != hipSuccess) return 1;
+    float ms = 0;
+    if (time_launches(reps, [&] { return zd::launch_yfft_variant(variant, S, nplanes, d_tw, d, 0); }, &ms)) return 1;
+    *ms_per_launch = ms / reps;
+    return 0;
 }
 
 int zd_test_copy_bw(int64_t bytes, int32_t reps, double *gbps) {
-    void *a = nullptr, *b = nullptr;
-    int rc = 1;
-    do {
-        if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess) break;
-        hipMemset(a, 1, bytes);
-        hipEvent_t e0, e1;
-        hipEventCreate(&e0);
-        hipEventCreate(&e1);
-        zd::launch_copy16(a, b, bytes / 16, 0);
-        hipEventRecord(e0, 0);
-        for (int i = 0; i < reps; i++) zd::launch_copy16(a, b, bytes / 16, 0);
-        hipEventRecord(e1, 0);
-        hipEventSynchronize(e1);
-        float ms = 0;
-        hipEventElapsedTime(&ms, e0, e1);
-        *gbps = 2.0 * bytes * reps / (ms * 1e-3) / 1e9;
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-        rc = 0;
-    } while (0);
-    hipFree(a);
-    hipFree(b);
-    return rc;
+    DevBuf<void> a, b;
+    if (a.alloc((size_t) bytes) != hipSuccess || b.alloc((size_t) bytes) != hipSuccess || hipMemset(a, 1, (size_t) bytes) != hipSuccess) return 1;
+    float ms = 0;
+    if (time_launches(reps, [&] { return zd::launch_copy16(a, b, bytes / 16, 0); }, &ms)) return 1;
+    *gbps = 2.0 * bytes * reps / (ms * 1e-3) / 1e9;
+    return 0;
 }
 
 #endif  // ZD_TUNING

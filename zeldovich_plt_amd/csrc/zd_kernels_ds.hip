@@ -253,11 +253,6 @@ int launch_ds_reduce(const double *partial, long long nwg, double *out, hipStrea
     return 0;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { hipFree(p); }
-};
-
 // what both entry points refuse before a plan or the GPU is touched; NULL: nothing
 const char *ds_refusal(const zd_params &p, int64_t nsites, const int64_t *sites, double *out7, char *buf, size_t cap) {
     if (!sites || !out7) return "zd_plan_direct_sum needs a site array and an output array";
@@ -305,8 +300,8 @@ extern "C" int zd_plan_direct_sum(zd_plan *pl, int64_t nsites, const int64_t *si
     constexpr int NV = DS_NS * DS_NQ;
     const int ngroups = (int) ((nsites + DS_NS - 1) / DS_NS);
     const long long nwg = (long long) ((N + DS_BX - 1) / DS_BX) * Hq;  // workgroups = partials of a launch group
-    DevBuf part, sums;
-    if (hipMalloc(&part.p, sizeof(double) * NV * (size_t) nwg) != hipSuccess || hipMalloc(&sums.p, sizeof(double) * NV * ngroups) != hipSuccess) {
+    zdown::DevBuf<double> part, sums;
+    if (part.alloc(NV * (size_t) nwg) != hipSuccess || sums.alloc((size_t) NV * ngroups) != hipSuccess) {
         fprintf(stderr, "zeldovich_hip: direct summation: no device memory for %lld partial sums\n", nwg * NV);
         return 1;
     }
@@ -321,7 +316,7 @@ extern "C" int zd_plan_direct_sum(zd_plan *pl, int64_t nsites, const int64_t *si
             const long double a = TWO_PI * (long double) S.z[s] / (long double) N;
             S.wr[s] = (double) cosl(a), S.wi[s] = (double) sinl(a);
         }
-        double *partial = (double *) part.p;
+        double *partial = part;
         const size_t per_row = (size_t) ((N + DS_BX - 1) / DS_BX) * NV;
         int rc = 0;
         if (fast) {  // the plane ky = 0 (rank 0) through the general form, every other row through the table arithmetic
@@ -331,10 +326,10 @@ extern "C" int zd_plan_direct_sum(zd_plan *pl, int64_t nsites, const int64_t *si
         } else {
             rc = launch_ds<false>(g, J, S, rank, G, Hq, pl->S.lG, pl->ec.vnorm, pl->d_twN, partial, st);
         }
-        if (rc || launch_ds_reduce(partial, nwg, (double *) sums.p + (size_t) grp * NV, st)) return 1;
+        if (rc || launch_ds_reduce(partial, nwg, sums + (size_t) grp * NV, st)) return 1;
     }
     std::vector<double> h((size_t) NV * ngroups);
-    if (hipMemcpyAsync(h.data(), sums.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    if (hipMemcpyAsync(h.data(), sums, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
         fprintf(stderr, "zeldovich_hip: direct summation failed: %s\n", hipGetErrorString(hipGetLastError()));
         return 1;
     }
@@ -366,7 +361,6 @@ extern "C" int zd_direct_sum(const zd_params *p_in, const zd_pk *pk, const doubl
     }
     zd_plan *pl = nullptr;
     if (zd_plan_create(&p, pk, eig, eig_ppd, 0, 1, &pl)) return 1;
-    const int rc = zd_plan_direct_sum(pl, nsites, sites_zyx, out7, nullptr);
-    zd_plan_destroy(pl);
-    return rc;
+    const zdown::PlanPtr plan(pl);
+    return zd_plan_direct_sum(pl, nsites, sites_zyx, out7, nullptr);
 }

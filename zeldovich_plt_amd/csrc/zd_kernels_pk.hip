@@ -217,11 +217,6 @@ int launch_pk(const GenConst &g, const SweepJumps &J, int ky_first, int ky_strid
     return 1;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { hipFree(p); }
-};
-
 }  // namespace
 
 extern "C" int zd_plan_measure_power(zd_plan *pl, int32_t bin_width, int64_t nbins, int64_t *count, double *sum_k, double *sum_dens,
@@ -258,13 +253,13 @@ extern "C" int zd_plan_measure_power(zd_plan *pl, int32_t bin_width, int64_t nbi
     }
     hipStream_t st = (hipStream_t) hip_stream;
     const size_t nb = (size_t) nbins;
-    DevBuf buf;
-    if (hipMalloc(&buf.p, nb * 8 * (1 + PK_NV)) != hipSuccess || hipMemsetAsync(buf.p, 0, nb * 8 * (1 + PK_NV), st) != hipSuccess) {
+    zdown::DevBuf<double> buf;  // counts (as uint64), then the PK_NV sums
+    if (buf.alloc(nb * (1 + PK_NV)) != hipSuccess || hipMemsetAsync(buf, 0, nb * 8 * (1 + PK_NV), st) != hipSuccess) {
         fprintf(stderr, "zeldovich_hip: band power: no device memory for %lld bins\n", (long long) nbins);
         return 1;
     }
-    unsigned long long *gcount = (unsigned long long *) buf.p;
-    double *gsum = (double *) buf.p + nb;
+    unsigned long long *gcount = (unsigned long long *) buf.get();
+    double *gsum = buf + nb;
     const SweepJumps J = zdsweep::make_sweep_jumps(pl->N);
     const int G = pl->nranks, rank = pl->rank, Hq = pl->Hq;  // rows ky = rank + G i, i < Hq
     const double vnorm2 = pl->ec.vnorm * pl->ec.vnorm;
@@ -279,7 +274,7 @@ extern "C" int zd_plan_measure_power(zd_plan *pl, int32_t bin_width, int64_t nbi
     }
     if (rc) return 1;
     std::vector<double> h(nb * (1 + PK_NV));
-    if (hipMemcpyAsync(h.data(), buf.p, nb * 8 * (1 + PK_NV), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    if (hipMemcpyAsync(h.data(), buf, nb * 8 * (1 + PK_NV), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
         fprintf(stderr, "zeldovich_hip: band power sweep failed: %s\n", hipGetErrorString(hipGetLastError()));
         return 1;
     }
@@ -311,7 +306,6 @@ extern "C" int zd_measure_power(const zd_params *p_in, const zd_pk *pk, const do
     }
     zd_plan *pl = nullptr;
     if (zd_plan_create(&p, pk, eig, eig_ppd, 0, 1, &pl)) return 1;
-    const int rc = zd_plan_measure_power(pl, bin_width, nbins, count, sum_k, sum_dens, sum_input, sum_disp, sum_vel, nullptr);
-    zd_plan_destroy(pl);
-    return rc;
+    const zdown::PlanPtr plan(pl);
+    return zd_plan_measure_power(pl, bin_width, nbins, count, sum_k, sum_dens, sum_input, sum_disp, sum_vel, nullptr);
 }

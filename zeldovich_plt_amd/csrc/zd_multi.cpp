@@ -35,6 +35,11 @@
 #endif
 
 using zdfft::cplx;
+using zdown::DevBuf;
+using zdown::Event;
+using zdown::PinnedBuf;
+using zdown::PlanPtr;
+using zdown::Stream;
 
 #define MHIP(call)                                                                                  \
     do {                                                                                            \
@@ -261,9 +266,9 @@ struct zd_comm {
     std::atomic<int> in_rccl{0};
     bool owns_nccl = false;  // zd_comm_create: this object aborts / destroys the communicator; thread-per-GPU driver: the driver does
     LocalGroup *grp = nullptr;
-    hipStream_t s_comm = nullptr;
-    hipEvent_t ev_z = nullptr, ev_x[2] = {nullptr, nullptr}, ev_r[2] = {nullptr, nullptr};
-    char *ring = nullptr;  // two slots of [source rank][planes of a group]...
+    Stream s_comm;
+    Event ev_z, ev_x[2], ev_r[2];
+    DevBuf<char> ring;  // two slots of [source rank][planes of a group]...
     int64_t ring_bytes = 0;  // bytes allocated at `ring`
     int64_t slot_bytes = 0;
     int group_planes = 0;
@@ -275,20 +280,20 @@ struct zd_comm {
     // per-rank accounting of the exchange (zd_comm_stats)
     int64_t bytes_sent = 0, bytes_received = 0;
     // pipelined passes (zd_plan_run_passes with two send stores): Z stage of a store complete / its sends complete
-    hipEvent_t ev_zd[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
+    Event ev_zd[2], ev_free[2];
     bool slot_used[2] = {false, false};  // an XY stage has been recorded on ev_x[slot] since the ring was (re)allocated
 };
 
 namespace {
 
 int comm_prepare(zd_comm *c) {
-    MHIP(hipStreamCreateWithFlags(&c->s_comm, hipStreamNonBlocking));
-    MHIP(hipEventCreateWithFlags(&c->ev_z, hipEventDisableTiming));
+    MHIP(c->s_comm.create());
+    MHIP(c->ev_z.create(hipEventDisableTiming));
     for (int i = 0; i < 2; i++) {
-        MHIP(hipEventCreateWithFlags(&c->ev_x[i], hipEventDisableTiming));
-        MHIP(hipEventCreateWithFlags(&c->ev_r[i], hipEventDisableTiming));
-        MHIP(hipEventCreateWithFlags(&c->ev_zd[i], hipEventDisableTiming));
-        MHIP(hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming));
+        MHIP(c->ev_x[i].create(hipEventDisableTiming));
+        MHIP(c->ev_r[i].create(hipEventDisableTiming));
+        MHIP(c->ev_zd[i].create(hipEventDisableTiming));
+        MHIP(c->ev_free[i].create(hipEventDisableTiming));
     }
     return 0;
 }
@@ -308,11 +313,10 @@ int comm_ring(zd_comm *c, int64_t ring_b, int gp, hipStream_t st) {
     if (c->ring) {
         MHIP(hipStreamSynchronize(st));
         MHIP(hipStreamSynchronize(c->s_comm));
-        MHIP(hipFree(c->ring));
-        c->ring       = nullptr;
+        c->ring.reset();
         c->ring_bytes = 0;
     }
-    MHIP(zd_store_alloc((void **) &c->ring, (size_t) ring_b));
+    MHIP(c->ring.store_alloc((size_t) ring_b));
     c->slot_used[0] = c->slot_used[1] = false;
     c->ring_bytes   = ring_b;
     c->slot_bytes   = ring_b / 2;
@@ -367,8 +371,8 @@ int zd_comm_create(int rank, int nranks, const void *id128, zd_comm **out) {
     // inside pass 0 with 200 GB of stores allocated.
     if (nranks > 1) {
         const size_t nb = (size_t) 1 << 20;
-        char *buf = nullptr;
-        bool ok = hipMalloc((void **) &buf, 2 * nb) == hipSuccess && hipMemsetAsync(buf, 0x5a, nb, c->s_comm) == hipSuccess;
+        DevBuf<char> buf;
+        bool ok = buf.alloc(2 * nb) == hipSuccess && hipMemsetAsync(buf, 0x5a, nb, c->s_comm) == hipSuccess;
         if (ok) {
             ok = R->GroupStart() == ncclSuccess;
             ok = ok && R->Send(buf, nb, ncclChar, (rank + 1) % nranks, c->nccl, c->s_comm) == ncclSuccess;
@@ -389,11 +393,10 @@ int zd_comm_create(int rank, int nranks, const void *id128, zd_comm **out) {
             fprintf(stderr, "zeldovich_hip: rank %d of %d: the 1 MB send / receive handshake with the neighbouring ranks failed or timed out: "
                             "the communicator is not usable\n", rank, nranks);
             zd_comm_abort(c);  // queued send / receive kernels drain
-            hipFree(buf);
+            buf.reset();
             zd_comm_destroy(c);
             return 1;
         }
-        hipFree(buf);
         c->bytes_sent = c->bytes_received = 0;
     }
     *out = c;
@@ -464,54 +467,46 @@ int zd_comm_probe(zd_comm *c, int64_t bytes_per_peer, int32_t reps, double *GBps
     if (!R) return 1;
     const int G = c->nranks, me = c->rank;
     const size_t nb = (size_t) bytes_per_peer;
-    char *sbuf = nullptr, *rbuf = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 1;
-    do {
-        if (hipMalloc((void **) &sbuf, nb * (size_t) (G - 1)) != hipSuccess || hipMalloc((void **) &rbuf, nb * (size_t) (G - 1)) != hipSuccess) break;
-        if (hipMemsetAsync(sbuf, 0x3c, nb * (size_t) (G - 1), c->s_comm) != hipSuccess) break;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) break;
-        bool ok = true;
-        for (int it = 0; it <= reps && ok; it++) {
-            if (it == 1) ok = hipEventRecord(e0, c->s_comm) == hipSuccess;  // (repetition 0 = warm-up: connection set-up)
-            RcclBlock blk(c);
-            if (!blk.h) {
-                ok = false;
-                break;
-            }
-            ok = ok && R->GroupStart() == ncclSuccess;
-            int slot = 0;
-            for (int p = 0; p < G && ok; p++) {
-                if (p == me) continue;
-                ok = R->Send(sbuf + nb * (size_t) slot, nb, ncclChar, p, blk.h, c->s_comm) == ncclSuccess
-                     && R->Recv(rbuf + nb * (size_t) slot, nb, ncclChar, p, blk.h, c->s_comm) == ncclSuccess;
-                slot++;
-            }
-            ok = (R->GroupEnd() == ncclSuccess) && ok;
-        }
-        ok = ok && hipEventRecord(e1, c->s_comm) == hipSuccess;
-        const auto t0 = std::chrono::steady_clock::now();
-        while (ok) {  // (bounded like the handshake: a link that does not come up must not hang the job)
-            const hipError_t q = hipStreamQuery(c->s_comm);
-            if (q == hipSuccess) break;
-            if (q != hipErrorNotReady || comm_failed(c) || std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) ok = false;
-            else std::this_thread::sleep_for(std::chrono::milliseconds(2));
-        }
-        if (!ok) {
-            fprintf(stderr, "zeldovich_hip: rank %d of %d: the link probe (%lld bytes to every peer) failed or timed out\n", me, G, (long long) bytes_per_peer);
-            zd_comm_abort(c);
+    DevBuf<char> sbuf, rbuf;
+    Event e0, e1;
+    if (sbuf.alloc(nb * (size_t) (G - 1)) != hipSuccess || rbuf.alloc(nb * (size_t) (G - 1)) != hipSuccess) return 1;
+    if (hipMemsetAsync(sbuf, 0x3c, nb * (size_t) (G - 1), c->s_comm) != hipSuccess) return 1;
+    if (e0.create() != hipSuccess || e1.create() != hipSuccess) return 1;
+    bool ok = true;
+    for (int it = 0; it <= reps && ok; it++) {
+        if (it == 1) ok = hipEventRecord(e0, c->s_comm) == hipSuccess;  // (repetition 0 = warm-up: connection set-up)
+        RcclBlock blk(c);
+        if (!blk.h) {
+            ok = false;
             break;
         }
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess || ms <= 0.f) break;
-        *GBps_per_peer = (double) nb * reps / (ms * 1e-3) / 1e9;
-        rc = 0;
-    } while (0);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    hipFree(sbuf);
-    hipFree(rbuf);
-    return rc;
+        ok = ok && R->GroupStart() == ncclSuccess;
+        int slot = 0;
+        for (int p = 0; p < G && ok; p++) {
+            if (p == me) continue;
+            ok = R->Send(sbuf + nb * (size_t) slot, nb, ncclChar, p, blk.h, c->s_comm) == ncclSuccess
+                 && R->Recv(rbuf + nb * (size_t) slot, nb, ncclChar, p, blk.h, c->s_comm) == ncclSuccess;
+            slot++;
+        }
+        ok = (R->GroupEnd() == ncclSuccess) && ok;
+    }
+    ok = ok && hipEventRecord(e1, c->s_comm) == hipSuccess;
+    const auto t0 = std::chrono::steady_clock::now();
+    while (ok) {  // (bounded like the handshake: a link that does not come up must not hang the job)
+        const hipError_t q = hipStreamQuery(c->s_comm);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady || comm_failed(c) || std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) ok = false;
+        else std::this_thread::sleep_for(std::chrono::milliseconds(2));
+    }
+    if (!ok) {
+        fprintf(stderr, "zeldovich_hip: rank %d of %d: the link probe (%lld bytes to every peer) failed or timed out\n", me, G, (long long) bytes_per_peer);
+        zd_comm_abort(c);
+        return 1;
+    }
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess || ms <= 0.f) return 1;
+    *GBps_per_peer = (double) nb * reps / (ms * 1e-3) / 1e9;
+    return 0;
 }
 
 void zd_comm_traffic(zd_comm *c, int64_t *bytes_sent, int64_t *bytes_received, int reset) {
@@ -523,16 +518,7 @@ void zd_comm_traffic(zd_comm *c, int64_t *bytes_sent, int64_t *bytes_received, i
 void zd_comm_destroy(zd_comm *c) {
     if (!c) return;
     if (c->nccl && c->owns_nccl && rccl() && rccl()->CommDestroy) rccl()->CommDestroy(c->nccl);
-    if (c->s_comm) hipStreamDestroy(c->s_comm);
-    if (c->ev_z) hipEventDestroy(c->ev_z);
-    for (int i = 0; i < 2; i++) {
-        if (c->ev_x[i]) hipEventDestroy(c->ev_x[i]);
-        if (c->ev_r[i]) hipEventDestroy(c->ev_r[i]);
-        if (c->ev_zd[i]) hipEventDestroy(c->ev_zd[i]);
-        if (c->ev_free[i]) hipEventDestroy(c->ev_free[i]);
-    }
-    hipFree(c->ring);
-    delete c;
+    delete c;  // (stream, events and ring release themselves)
 }
 
 // planes per exchange group and bytes of the two-slot ring that zd_plan_run_pass allocates on first use
@@ -744,9 +730,9 @@ static int run_passes_impl(zd_plan *pl, zd_comm *c, int first, int step, void *d
     // p - 1 have left that store.  Two stores of half the size mean twice the passes (twice the generations), so whether this
     // pays is a measurement: bench.py --two-stores (profiles/r04_tuning_notes.md).
     if (!pipelined && pl->nranks == 1 && d_store2 != nullptr && first + step < pl->npass && pl->overlap && !pl->any && !pl->dens_sub) {
-        for (hipEvent_t &e : pl->ev_pipe)
-            if (!e) MHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        hipEvent_t ev_start = pl->ev_pipe[0], *ev_zd = pl->ev_pipe + 1, *ev_xy = pl->ev_pipe + 3;
+        for (Event &e : pl->ev_pipe)
+            if (!e) MHIP(e.create(hipEventDisableTiming));
+        const hipEvent_t ev_start = pl->ev_pipe[0], ev_zd[2] = {pl->ev_pipe[1], pl->ev_pipe[2]}, ev_xy[2] = {pl->ev_pipe[3], pl->ev_pipe[4]};
         void *stores[2] = {d_store, d_store2};
         MHIP(hipEventRecord(ev_start, st));
         if (zd_plan_stage_z_detached(pl, first, stores[0], st, ev_start, ev_zd[0])) return 1;
@@ -768,23 +754,22 @@ static int run_passes_impl(zd_plan *pl, zd_comm *c, int first, int step, void *d
     }
     if (comm_failed(c)) return 1;
     void *stores[2] = {d_store, d_store2};
-    int rc = 0, i = 0;
-    do {
+    // (every failure in here must reach the abort epilogue below, or the peers spin in their queued send / receive kernels)
+    const int rc = [&]() -> int {
         // the first Z stage starts after whatever the caller queued on its stream (the stores' previous users)
-        // (no MHIP in this block: a failure must reach the abort epilogue below, or the peers spin in their queued send / receive kernels)
-        if (hipEventRecord(c->ev_z, st) != hipSuccess) { rc = 1; break; }
-        if ((rc = zd_plan_stage_z_detached(pl, first, stores[0], st, c->ev_z, c->ev_zd[0]))) break;
-        for (int pass = first; pass < pl->npass && !rc; pass += step, i++) {
+        if (hipEventRecord(c->ev_z, st) != hipSuccess) return 1;
+        if (zd_plan_stage_z_detached(pl, first, stores[0], st, c->ev_z, c->ev_zd[0])) return 1;
+        int i = 0;
+        for (int pass = first; pass < pl->npass; pass += step, i++) {
             const int b = i & 1, nxt = pass + step;
-            if (nxt < pl->npass)  // store 1-b was last read by the sends of pass i-1 (ev_free); the very first use is free
-                if ((rc = zd_plan_stage_z_detached(pl, nxt, stores[1 - b], st, i >= 1 ? c->ev_free[1 - b] : c->ev_z, c->ev_zd[1 - b]))) break;
+            // store 1-b was last read by the sends of pass i-1 (ev_free); the very first use is free
+            if (nxt < pl->npass && zd_plan_stage_z_detached(pl, nxt, stores[1 - b], st, i >= 1 ? c->ev_free[1 - b] : c->ev_z, c->ev_zd[1 - b])) return 1;
             pc.pass = pass;
-            rc = run_pass_body(pl, c, pass, stores[b], d_records, d_density, rec_planes, pass_cb_adaptor, &pc, st, c->ev_zd[b], c->ev_free[b]);
+            if (run_pass_body(pl, c, pass, stores[b], d_records, d_density, rec_planes, pass_cb_adaptor, &pc, st, c->ev_zd[b], c->ev_free[b])) return 1;
         }
-        if (rc) break;
         // the caller's stream ends behind the last sends (the stores may be freed or rewritten by the caller afterwards)
-        if (hipEventRecord(c->ev_z, c->s_comm) != hipSuccess || hipStreamWaitEvent(st, c->ev_z, 0) != hipSuccess) rc = 1;
-    } while (0);
+        return hipEventRecord(c->ev_z, c->s_comm) != hipSuccess || hipStreamWaitEvent(st, c->ev_z, 0) != hipSuccess;
+    }();
     if (rc) {
         if (c->failed) c->failed->store(1, std::memory_order_release);
         zd_comm_abort(c);
@@ -1046,9 +1031,10 @@ int zd_generate_multi(const zd_params *p_in, const zd_pk *pk, const double *eig,
     // here): the send / receive kernels its peers have queued for it drain instead of spinning, the peers' stream syncs
     // return, they see the flag and leave.  Aborted communicators are freed by the abort, not destroyed again.
     // (the abort FREES a communicator, and a healthy rank thread may be about to enter RCCL with the same handle —
-    // every rank's zd_comm lives for the whole job, owned by this driver, and its `nccl_mu` is held around each group of RCCL
-    // host calls of its rank and around the abort of its communicator; after the abort the handle is gone from the zd_comm
-    // and the rank's next exchange returns 1 before touching RCCL.)
+    // every rank's zd_comm lives for the whole job, owned by this driver; its `nccl_mu` is held only to publish, fetch or take
+    // away the handle and to count the rank into a block of RCCL host calls (RcclBlock), never across the calls or the abort
+    // themselves (zd_comm::nccl_mu); after the abort the handle is gone from the zd_comm and the rank's next exchange returns
+    // 1 before touching RCCL.)
     std::atomic<int> job_failed{0};
     std::mutex abort_mu;
     bool aborted = false;
@@ -1086,17 +1072,18 @@ int zd_generate_multi(const zd_params *p_in, const zd_pk *pk, const double *eig,
         ctx[g].device = g % ndev;
         threads.emplace_back([&, g]() {
             RankCtx &me = ctx[g];
-            me.rc       = 1;
-            zd_plan *pl = nullptr;
-            void *d_store = nullptr, *d_store2 = nullptr, *d_rec = nullptr;
-            float *d_dens = nullptr, *h_dens = nullptr;
-            void *d_phik = nullptr;
-            char *h_rec = nullptr;
             zd_comm *c  = comms[g];
-            hipStream_t st = nullptr;
-            do {
-                if (hipSetDevice(me.device) != hipSuccess) break;
-                if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) break;
+            // what this rank holds: released at the end of this function — on the rank's thread, its device current, and after
+            // abort_all() below has let the peers go — the stream first and the plan last
+            PlanPtr plan;
+            DevBuf<cplx> d_phik;  // f_NL: PhiK of this rank's rows, until the main plan exists and owns it
+            PinnedBuf<float> h_dens;
+            PinnedBuf<char> h_rec;
+            DevBuf<float> d_dens;
+            DevBuf<void> d_rec, d_store2, d_store;
+            Stream st;
+            me.rc = [&]() -> int {
+                if (hipSetDevice(me.device) != hipSuccess || st.create() != hipSuccess) return 1;
                 const int grp_id = g / gsz, rk = g % gsz;  // group, rank inside it
                 c->rank   = rk;
                 c->nranks = gsz;
@@ -1107,35 +1094,35 @@ int zd_generate_multi(const zd_params *p_in, const zd_pk *pk, const double *eig,
                 }
                 c->grp    = &grps[grp_id];
                 c->failed = &job_failed;
-                if (comm_prepare(c)) break;
+                if (comm_prepare(c)) return 1;
 #ifdef ZD_TESTING
                 if (g_test_fail_rank.load() == g) {  // a rank that fails BEFORE its first exchange (store allocation, plan error):
                     fprintf(stderr, "zeldovich_hip: (test) rank %d fails before pass 0\n", g);  // its peers sit in their first GroupEnd
-                    break;
+                    return 1;
                 }
 #endif
+                zd_plan *pl = nullptr;
                 if (p.f_NL != 0.) {  // the phi round first (its own plan, store and ring), then the main plan reads PhiK
-                    zd_plan *ph = nullptr;
-                    void *d_phi = nullptr;
-                    bool ok     = false;
-                    do {
-                        if (zd_plan_create_phi(&p, pk, rk, gsz, &ph)) break;
-                        if (zd_store_alloc(&d_phi, (size_t) zd_plan_exchange_bytes(ph)) != hipSuccess
-                            || zd_store_alloc(&d_phik, (size_t) ph->Hq * ph->N * ph->N * 16) != hipSuccess) {
+                    {
+                        zd_plan *ph = nullptr;
+                        if (zd_plan_create_phi(&p, pk, rk, gsz, &ph)) return 1;
+                        PlanPtr phi_plan(ph);
+                        DevBuf<void> d_phi;
+                        if (d_phi.store_alloc((size_t) zd_plan_exchange_bytes(ph)) != hipSuccess
+                            || d_phik.store_alloc((size_t) ph->Hq * ph->N * ph->N) != hipSuccess) {
                             fprintf(stderr, "zeldovich_hip: rank %d: f_NL needs %.1f GB of HBM for the phi field\n", g,
                                     (zd_plan_exchange_bytes(ph) + (double) ph->Hq * ph->N * ph->N * 16) / 1e9);
-                            break;
+                            return 1;
                         }
                         if (g == 0) fprintf(stderr, "Generating phi field\n");
-                        if (phi_round(ph, c, d_phi, d_phik, p.f_NL, st)) break;
-                        ok = true;
-                    } while (0);
-                    hipFree(d_phi);
-                    if (ph) zd_plan_destroy(ph);
-                    if (!ok) break;
-                    if (zd_plan_create_phik(&p, pk, eig, eig_ppd, rk, gsz, d_phik, &pl)) break;
-                } else if (zd_plan_create(&p, pk, eig, eig_ppd, rk, gsz, &pl)) {
-                    break;
+                        if (phi_round(ph, c, d_phi, d_phik, p.f_NL, st)) return 1;
+                    }
+                    if (zd_plan_create_phik(&p, pk, eig, eig_ppd, rk, gsz, d_phik, &pl)) return 1;
+                    plan.reset(pl);
+                    pl->d_phik_owned = std::move(d_phik);
+                } else {
+                    if (zd_plan_create(&p, pk, eig, eig_ppd, rk, gsz, &pl)) return 1;
+                    plan.reset(pl);
                 }
                 const int ps = pl->pstep;
                 const bool want_rec = pl->narray >= 2 && !pl->dens_only, want_dens = p.qdensity != 0;  // ZD_qdensity = 2: density only
@@ -1144,17 +1131,17 @@ int zd_generate_multi(const zd_params *p_in, const zd_pk *pk, const double *eig,
                 const int64_t ring_b = cb ? ((int64_t) 1 << 30) : ((int64_t) 4 << 30);
                 int64_t rec_planes = std::max<int64_t>(ps, std::min<int64_t>(zd_plan_local_planes(pl),
                                                                              ring_b / (int64_t) (plane_rec_b + (want_dens ? nn * 4 : 0))) / ps * ps);
-                if (zd_store_alloc(&d_store, (size_t) zd_plan_exchange_bytes(pl)) != hipSuccess) {
+                if (d_store.store_alloc((size_t) zd_plan_exchange_bytes(pl)) != hipSuccess) {
                     fprintf(stderr, "zeldovich_hip: rank %d cannot allocate the %.2f GB block store\n", g, zd_plan_exchange_bytes(pl) / 1e9);
-                    break;
+                    return 1;
                 }
-                if (want_rec && hipMalloc(&d_rec, plane_rec_b * (size_t) rec_planes) != hipSuccess) break;
-                if (want_rec && cb && hipHostMalloc((void **) &h_rec, plane_rec_b * (size_t) rec_planes) != hipSuccess) break;
-                if (want_dens && hipMalloc((void **) &d_dens, nn * 4 * (size_t) rec_planes) != hipSuccess) break;
-                if (want_dens && cb && hipHostMalloc((void **) &h_dens, nn * 4 * (size_t) rec_planes) != hipSuccess) break;
+                if (want_rec && d_rec.alloc(plane_rec_b * (size_t) rec_planes) != hipSuccess) return 1;
+                if (want_rec && cb && h_rec.alloc(plane_rec_b * (size_t) rec_planes) != hipSuccess) return 1;
+                if (want_dens && d_dens.alloc(nn * (size_t) rec_planes) != hipSuccess) return 1;
+                if (want_dens && cb && h_dens.alloc(nn * (size_t) rec_planes) != hipSuccess) return 1;
                 if (pl->npass % groups) {
                     fprintf(stderr, "zeldovich_hip: %d passes do not deal out over %d pass groups\n", pl->npass, groups);
-                    break;
+                    return 1;
                 }
                 // sum |D|^2 of the packed stores comes from the generator, once per run and rank: every group sees every
                 // mode, so only group 0 accumulates it (its ranks cover all rows between them)
@@ -1165,24 +1152,14 @@ int zd_generate_multi(const zd_params *p_in, const zd_pk *pk, const double *eig,
                     size_t free_b = 0, total_b = 0;
                     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess
                         && free_b > (size_t) zd_plan_exchange_bytes(pl) * ((G + ndev - 1) / ndev) + ((size_t) 12 << 30))
-                        if (zd_store_alloc(&d_store2, (size_t) zd_plan_exchange_bytes(pl)) != hipSuccess) d_store2 = nullptr;
+                        d_store2.store_alloc((size_t) zd_plan_exchange_bytes(pl));  // (no second store: the passes run one after the other)
                 }
-                GroupSink sink{pl, grp_id, &dl, h_rec, plane_rec_b, cb ? d_dens : nullptr, h_dens, -1, &job_failed, &job_failed};
-                if (run_passes_impl(pl, c, grp_id, groups, d_store, d_store2, d_rec, d_dens, rec_planes, sink_cb, &sink, st)) break;
-                if (zd_plan_stats(pl, &me.stats)) break;
-                if (job_failed.load(std::memory_order_acquire)) break;  // a peer failed: this rank's planes are not a result
-                me.rc = 0;
-            } while (0);
+                GroupSink sink{pl, grp_id, &dl, h_rec, plane_rec_b, cb ? d_dens.get() : nullptr, h_dens, -1, &job_failed, &job_failed};
+                if (run_passes_impl(pl, c, grp_id, groups, d_store, d_store2, d_rec, d_dens, rec_planes, sink_cb, &sink, st)) return 1;
+                if (zd_plan_stats(pl, &me.stats)) return 1;
+                return job_failed.load(std::memory_order_acquire) != 0;  // a peer failed: this rank's planes are not a result
+            }();
             if (me.rc) abort_all();
-            if (st) hipStreamDestroy(st);
-            hipFree(d_store);
-            hipFree(d_store2);
-            hipFree(d_rec);
-            hipFree(d_dens);
-            hipFree(d_phik);
-            if (h_rec) hipHostFree(h_rec);
-            if (h_dens) hipHostFree(h_dens);
-            if (pl) zd_plan_destroy(pl);
         });
     }
     for (auto &t : threads) t.join();

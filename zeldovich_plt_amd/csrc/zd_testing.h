@@ -16,6 +16,9 @@ int zd_test_route(const zd_params *p, int32_t R, int32_t nranks, int32_t *out, c
 /* the coefficients a ZD_q2LPT job runs with (zd_route.h): out[0 .. 2] = alpha (= vnorm), lpt2_ratio and lpt2_f2 with their defaults
  * resolved */
 void zd_test_lpt2_coefficients(const zd_params *p, double *out);
+/* device buffers, pinned buffers, events and streams the library's owning handles (zd_own.h) hold at this moment, plus the plans alive:
+ * 0 once everything the library made has been given back */
+int64_t zd_test_live_handles(void);
 /* ---- device test hooks (each needs a GPU) -------------------- */
 /* n counter-addressed draws: out[2*i], out[2*i+1] = the two uint64 of mode (kx,ky,kz)[i] */
 int zd_test_draws(int64_t seed, int64_t n, const int32_t *kxyz, uint64_t *out);
