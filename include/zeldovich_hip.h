@@ -284,8 +284,16 @@ typedef struct zd_param_strings {
     double SelfCheck_tol;
     int32_t SelfCheck;
     char SelfCheck_filename[1024];
+    /* ZD_PLT_compute_ppd = n (optional, not in the reference): with ZD_qPLT = 1 the CLI computes the eigenmode table of n points per
+     * side on the GPU (zd_make_eigenmodes) instead of loading ZD_PLT_filename; exactly one of the two must be given, and n must be one
+     * zd_make_eigenmodes accepts.  The member fills what was the padding at the end of the struct: its size is unchanged.
+     * (ZD_PLT_write_filename, the file the CLI writes the table it used to, is read with zd_param_file_string.) */
+    int32_t PLT_compute_ppd;
 } zd_param_strings;
 int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s);
+/* The string a parameter file assigns to `key`, unquoted, into value[cap]; "" if the file does not assign it.  Non-zero (message) if the
+ * file cannot be read or the string does not fit.  For optional keys that have no member in zd_param_strings (ZD_PLT_write_filename). */
+int zd_param_file_string(const char *path, const char *key, char *value, int64_t cap);
 
 /* PowerSpectrum: InitFromFile / InitFromPowerLaw + Normalize.  The handle owns the tables that
  * zd_pk points into. */
@@ -302,6 +310,18 @@ void zd_pk_destroy(zd_pk_handle *h);
 /* load_eigmodes: src/zeldovich.cpp:794-830.  Caller frees with zd_free. */
 int zd_load_eigmodes(const char *path, double **eig, int64_t *eig_ppd);
 void zd_free(void *p);
+/* The inverse of zd_load_eigmodes: an int32 n followed by the n * n * (n/2 + 1) * 4 doubles of eig (no GPU needed).  A computed table
+ * can then feed the reference program or a later run. */
+int zd_write_eigmodes(const char *path, const double *eig, int64_t n);
+
+/* ---- the PLT eigenmode table, computed ---------------------------------------------------------
+ * Fills the HOST array eig[n][n][n/2 + 1][4] = (e_x, e_y, e_z, lambda) with the eigenmode table of the simple cubic lattice under
+ * periodic gravity (Marcos et al. 2006): per wavevector the dynamical matrix as an Ewald sum and the most longitudinal eigenmode; the
+ * definition is pinned in csrc/zd_kernels_plt.hip.  This is the table zd_generate takes as eig / eig_ppd = n; a run whose PPD is a
+ * multiple of n reads it directly, any other interpolates (src/zeldovich.cpp:149-276).  n: even, in [4, ZD_PLT_MAX_PPD]; anything else
+ * is refused (message, non-zero) before the array or the GPU is touched.  Two calls return the same bits. */
+#define ZD_PLT_MAX_PPD 512
+int zd_make_eigenmodes(int64_t n, double *eig);
 
 /* ---- band power of the realised modes ---------------------------------------------------------
  * One sweep over the modes a run generates (no transform, no store) that bins instead of storing; the definition is pinned in

@@ -69,6 +69,7 @@ class ZdParamStrings(C.Structure):
         ("f_NL", C.c_double), ("n_s", C.c_double), ("Omega_M", C.c_double), ("np", C.c_int64),
         ("Pk_measured_filename", C.c_char * 1024),
         ("SelfCheck_tol", C.c_double), ("SelfCheck", C.c_int32), ("SelfCheck_filename", C.c_char * 1024),
+        ("PLT_compute_ppd", C.c_int32),
     ]
 
 
@@ -84,11 +85,11 @@ EXPORTED_SYMBOLS = [
     "zd_params_from_file", "zd_pk_create_from_file", "zd_pk_create_powerlaw", "zd_pk_power",
     "zd_pk_sigmaR", "zd_pk_destroy", "zd_load_eigmodes", "zd_free", "zd_comm_abort", "zd_comm_traffic", "zd_choose_pass_groups", "zd_plan_run_passes", "zd_comm_probe", "zd_choose_pass_groups_measured",
     "zd_dispatch_report", "zd_power_nbins", "zd_plan_measure_power", "zd_measure_power",
-    "zd_plan_direct_sum", "zd_direct_sum",
+    "zd_plan_direct_sum", "zd_direct_sum", "zd_make_eigenmodes", "zd_write_eigmodes", "zd_param_file_string",
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
-                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route", "zd_test_lpt2_coefficients", "zd_test_live_handles"]
+                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route", "zd_test_lpt2_coefficients", "zd_test_live_handles", "zd_test_plt_matrix"]
 STORE_MODES = {"auto": 0, "reference": 1, "packed": 2, "fields": 3}  # zd_params.store_mode (ZD_STORE_*)
 
 _lib = None
@@ -141,6 +142,7 @@ def _load(path, testing):
         L.zd_test_lpt2_coefficients.restype = None
         L.zd_test_live_handles.argtypes = []
         L.zd_test_live_handles.restype = i64
+        L.zd_test_plt_matrix.argtypes = [i64, dbl, i32, i64, vp, vp]
     L.zd_choose_stream_factor.argtypes = [C.POINTER(ZdParams), C.c_int, i64]
     L.zd_choose_pass_groups.argtypes = [C.POINTER(ZdParams), C.c_int, i64, C.POINTER(i32), C.POINTER(i32)]
     L.zd_plan_create.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, C.c_int, C.c_int, C.POINTER(vp)]
@@ -173,6 +175,7 @@ def _load(path, testing):
     L.zd_plan_run_pass.argtypes = [vp, vp, C.c_int, vp, vp, i64, GROUP_CB, vp, vp]
     L.zd_plan_run_passes.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, i64, PASS_CB, vp, vp]
     L.zd_params_from_file.argtypes = [C.c_char_p, C.POINTER(ZdParams), C.POINTER(ZdParamStrings)]
+    L.zd_param_file_string.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, i64]
     L.zd_pk_create_from_file.argtypes = [C.c_char_p, dbl, dbl, dbl, dbl, dbl, C.c_int, dbl, C.POINTER(vp), C.POINTER(ZdPk)]
     L.zd_pk_create_powerlaw.argtypes = [dbl, dbl, dbl, dbl, dbl, C.c_int, dbl, C.POINTER(vp), C.POINTER(ZdPk)]
     L.zd_pk_power.argtypes = [C.POINTER(ZdPk), dbl]
@@ -184,6 +187,8 @@ def _load(path, testing):
     L.zd_load_eigmodes.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(i64)]
     L.zd_free.argtypes = [vp]
     L.zd_free.restype = None
+    L.zd_write_eigmodes.argtypes = [C.c_char_p, vp, i64]
+    L.zd_make_eigenmodes.argtypes = [i64, vp]
     L.zd_power_nbins.argtypes = [i64, i32]
     L.zd_power_nbins.restype = i64
     L.zd_plan_measure_power.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp]
@@ -261,6 +266,14 @@ def params_from_file(path):
     if L.zd_params_from_file(os.fsencode(path), C.byref(p), C.byref(s)):
         raise ValueError("Invalid Parameters given: %s" % path)
     return p, s
+
+
+def param_file_string(path, key):
+    """the string a parameter file assigns to `key` (zd_param_file_string); "" if it does not"""
+    buf = C.create_string_buffer(1024)
+    if load_library().zd_param_file_string(os.fsencode(path), key.encode(), buf, len(buf)):
+        raise ValueError("parameter file %s: %s could not be read" % (path, key))
+    return os.fsdecode(buf.value)
 
 
 class PowerSpectrum:
@@ -363,6 +376,44 @@ def generate(params, ps, eig=None, collect=True, loopback=False, testing=False):
         raise RuntimeError("zd_generate failed (rc=%d); see stderr" % rc)
     out.update(_stats_dict(st))
     return out
+
+
+PLT_MAX_PPD = 512  # ZD_PLT_MAX_PPD
+
+
+def make_eigenmodes(n):
+    """The PLT eigenmode table of n points per side, computed on cuda:0 (zd_make_eigenmodes; definition in csrc/zd_kernels_plt.hip):
+    float64 [n][n][n/2 + 1][4] = (e_x, e_y, e_z, lambda), what generate / Plan / measure_power / direct_sum take as eig.  n: even, in
+    [4, 512]."""
+    n = int(n)
+    if n < 4 or n > PLT_MAX_PPD or n % 2:
+        raise ValueError("make_eigenmodes: n must be even and in [4, %d] (got %d)" % (PLT_MAX_PPD, n))
+    out = np.empty((n, n, n // 2 + 1, 4), dtype=np.float64)
+    if load_library().zd_make_eigenmodes(n, out.ctypes.data):
+        raise RuntimeError("zd_make_eigenmodes failed; see stderr")
+    return out
+
+
+def write_eigenmodes(path, table):
+    """an eigenmode table [n][n][n/2 + 1][4] as the file ZD_PLT_filename names (zd_write_eigmodes: int32 n, then the doubles)"""
+    t = np.ascontiguousarray(table, dtype=np.float64)
+    if t.ndim != 4 or t.shape[1] != t.shape[0] or t.shape[2] != t.shape[0] // 2 + 1 or t.shape[3] != 4:
+        raise ValueError("write_eigenmodes: the table must be [n][n][n/2 + 1][4] (got %r)" % (t.shape,))
+    if load_library().zd_write_eigmodes(os.fsencode(path), t.ctypes.data, t.shape[0]):
+        raise RuntimeError("zd_write_eigmodes failed; see stderr")
+
+
+def load_eigenmodes(path):
+    """the table of an eigenmode file (zd_load_eigmodes), as an array [n][n][n/2 + 1][4]"""
+    L = load_library()
+    ptr, n = C.c_void_p(), C.c_int64()
+    if L.zd_load_eigmodes(os.fsencode(path), C.byref(ptr), C.byref(n)):
+        raise RuntimeError("zd_load_eigmodes failed; see stderr")
+    try:
+        shape = (n.value, n.value, n.value // 2 + 1, 4)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_double)), shape).copy()
+    finally:
+        L.zd_free(ptr)
 
 
 POWER_SUMS = ("sum_k", "sum_dens", "sum_input", "sum_disp", "sum_vel")
@@ -627,6 +678,17 @@ def test_modes_table(params, ps, kxyz):
     if L.zd_test_modes_table(C.byref(params), C.byref(ps.pk), k.shape[0], k.ctypes.data, out.ctypes.data):
         raise RuntimeError("zd_test_modes_table failed")
     return out[:, 0] + 1j * out[:, 1], out[:, 2]
+
+
+def test_plt_matrix(n, m_xyz, alpha=2.0, shells=4):
+    """the six distinct elements xx, yy, zz, xy, xz, yz of the PLT dynamical matrix at the signed wavenumbers m_xyz [nmodes, 3] of a
+    table of n points per side (zd_test_plt_matrix)"""
+    L = load_testing_library()
+    m = np.ascontiguousarray(m_xyz, dtype=np.int32).reshape(-1, 3)
+    out = np.zeros((m.shape[0], 6), dtype=np.float64)
+    if L.zd_test_plt_matrix(int(n), float(alpha), int(shells), m.shape[0], m.ctypes.data, out.ctypes.data):
+        raise RuntimeError("zd_test_plt_matrix failed")
+    return out
 
 
 def test_v1_words(seed, nblocks):

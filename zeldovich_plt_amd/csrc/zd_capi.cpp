@@ -20,6 +20,7 @@
 #include "zd_launch.h"
 #include "zd_plan.h"
 #include "zd_route.h"
+#include "zd_plt.h"
 #ifdef ZD_TUNING
 #include "zd_tuning.h"
 #endif
@@ -2062,6 +2063,43 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the PLT eigenmode table (definition and kernels: zd_kernels_plt.hip)
+
+// what zd_make_eigenmodes (and the parameter reader, zd_host.cpp) refuses; NULL: nothing
+static const char *plt_table_refusal(int64_t n, char *buf, size_t cap) {
+    if (n >= 4 && n <= ZD_PLT_MAX_PPD && n % 2 == 0) return nullptr;
+    snprintf(buf, cap, "an eigenmode table has an even number of points per side in [4, %d] (got %lld)", ZD_PLT_MAX_PPD, (long long) n);
+    return buf;
+}
+
+int zd_make_eigenmodes(int64_t n, double *eig) {
+    char buf[160];
+    if (const char *why = plt_table_refusal(n, buf, sizeof(buf))) {
+        fprintf(stderr, "zeldovich_hip: zd_make_eigenmodes: %s\n", why);
+        return 1;
+    }
+    if (!eig) {
+        fprintf(stderr, "zeldovich_hip: zd_make_eigenmodes needs an output array\n");
+        return 1;
+    }
+    const zd::PltConst c = zd::plt_const((int) n, zd::PLT_ALPHA);
+    const size_t plane = (size_t) n * (n / 2 + 1) * 4;  // doubles of one kx plane
+    // chunks of kx planes of at most 2^21 wavevectors (64 MB): a table of 512 points is 2.2 GB and 7e7 threads
+    const int chunk = (int) std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t) 1 << 23) / (int64_t) plane));
+    DevBuf<double> d_tab, d_out;
+    if (upload(d_tab, zd::plt_shell_table(zd::PLT_ALPHA, zd::PLT_SHELLS)) != hipSuccess || d_out.alloc(plane * chunk) != hipSuccess) {
+        fprintf(stderr, "zeldovich_hip: zd_make_eigenmodes: no device memory for %zu bytes (is there a GPU?)\n", plane * chunk * sizeof(double));
+        return 1;
+    }
+    for (int kx0 = 0; kx0 < n; kx0 += chunk) {
+        const int nkx = std::min<int>(chunk, (int) n - kx0);
+        if (zd::launch_plt_modes(c, d_tab, kx0, nkx, d_out, 0)) return 1;
+        HIPCHECK(hipMemcpy(eig + plane * kx0, d_out, plane * nkx * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
 #ifdef ZD_TESTING
 // ------------------------------------------------------------------------------------------------
 // device test hooks
@@ -2204,6 +2242,25 @@ int zd_test_fft(int32_t n, int64_t lines, int32_t axis_kind, const double *in, d
     }
     return test_fft_run(make_twiddles(n), nel, false, in, out,
                         [&](const cplx *tw, cplx *i, cplx *o) { return zd::launch_test_fft(n, axis_kind, tw, i, o, lines, 0); });
+}
+
+int zd_test_plt_matrix(int64_t n, double alpha, int32_t shells, int64_t nmodes, const int32_t *m_xyz, double *out6) {
+    if (n < 1 || n > (1 << 20) || !(alpha > 0.) || shells < 3 || shells > 5 || nmodes < 1 || !m_xyz || !out6) {
+        fprintf(stderr, "zd_test_plt_matrix: n in [1, 2^20], alpha > 0, shells 3, 4 or 5, at least one mode\n");
+        return 1;
+    }
+    for (int64_t i = 0; i < 3 * nmodes; i++)
+        if (m_xyz[i] < -n || m_xyz[i] > n) {
+            fprintf(stderr, "zd_test_plt_matrix: wavenumber %d outside [-n, n]\n", (int) m_xyz[i]);
+            return 1;
+        }
+    DevBuf<double> d_tab, d_o;
+    DevBuf<int> d_m;
+    if (upload(d_tab, zd::plt_shell_table(alpha, shells)) != hipSuccess || upload(d_m, (const int *) m_xyz, 3 * (size_t) nmodes) != hipSuccess ||
+        d_o.alloc(6 * (size_t) nmodes) != hipSuccess)
+        return 1;
+    if (zd::launch_test_plt_matrix(zd::plt_const((int) n, alpha), shells, d_tab, nmodes, d_m, d_o, 0)) return 1;
+    return hipMemcpy(out6, d_o, sizeof(double) * 6 * (size_t) nmodes, hipMemcpyDeviceToHost) != hipSuccess;
 }
 
 #endif  // ZD_TESTING

@@ -301,6 +301,27 @@ int zd_load_eigmodes(const char *path, double **eig, int64_t *eig_ppd) {
 }
 void zd_free(void *p) { free(p); }
 
+// the inverse of zd_load_eigmodes
+int zd_write_eigmodes(const char *path, const double *eig, int64_t n) {
+    if (!path || !eig || n < 1 || n > std::numeric_limits<int32_t>::max()) {
+        fprintf(stderr, "[Error] zd_write_eigmodes needs a path, a table and its number of points per side.\n");
+        return 1;
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) {
+        fprintf(stderr, "[Error] Could not open eigenmode file \"%s\" for writing.\n", path);
+        return 1;
+    }
+    const int32_t n32  = (int32_t) n;
+    const size_t nelem = (size_t) n * n * (n / 2 + 1) * 4;
+    const bool ok      = fwrite(&n32, sizeof(n32), 1, f) == 1 && fwrite(eig, sizeof(double), nelem, f) == nelem;
+    if (fclose(f) != 0 || !ok) {
+        fprintf(stderr, "[Error] Could not write %zu bytes to eigenmode file \"%s\".\n", nelem * sizeof(double) + sizeof(n32), path);
+        return 1;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // parameter file
 
@@ -525,6 +546,19 @@ int64_t zd_power_nbins(int64_t ppd, int32_t bin_width) {
     return r / bin_width + 1;
 }
 
+int zd_param_file_string(const char *path, const char *key, char *value, int64_t cap) {
+    HeaderState H;
+    if (!path || !key || !value || cap < 1 || read_statements(path, H, 0)) return 1;
+    const auto it       = H.kv.find(key);
+    const std::string v = it == H.kv.end() ? std::string() : unquote(it->second);
+    if ((int64_t) v.size() >= cap) {
+        fprintf(stderr, "Parameter \"%s\" in \"%s\" is longer than %lld characters\n", key, path, (long long) cap - 1);
+        return 1;
+    }
+    memcpy(value, v.c_str(), v.size() + 1);
+    return 0;
+}
+
 int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     HeaderState H;
     if (read_statements(path, H, 0)) return 1;
@@ -637,6 +671,8 @@ int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     I("ZD_SelfCheck", s->SelfCheck);
     D("ZD_SelfCheck_tol", s->SelfCheck_tol);
     S("ZD_SelfCheck_filename", s->SelfCheck_filename, sizeof(s->SelfCheck_filename));
+    // the eigenmode table computed instead of loaded (csrc/zd_kernels_plt.hip)
+    I("ZD_PLT_compute_ppd", s->PLT_compute_ppd);
     (void) have_cpd;
     p->cpd = cpd;
 
@@ -685,7 +721,19 @@ int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     ZD_REQUIRE(p->f_cluster > 0. && p->f_cluster <= 1.);
     ZD_REQUIRE((s->Pk_filename[0] != 0) != (bool) (s->Pk_powerlaw_index != 1000));
     if (s->Pk_powerlaw_index != 1000) ZD_REQUIRE(s->Pk_powerlaw_index <= 0);
-    if (p->qPLT) ZD_REQUIRE(s->PLT_filename[0] != 0);
+    if (p->qPLT && has("ZD_PLT_compute_ppd")) {  // what zd_make_eigenmodes refuses is refused here
+        const int32_t n = s->PLT_compute_ppd;
+        if (s->PLT_filename[0]) {
+            fprintf(stderr, "Invalid Parameters given: ZD_PLT_compute_ppd and ZD_PLT_filename are both given: the table is either computed or loaded\n");
+            return 1;
+        }
+        if (n < 4 || n > ZD_PLT_MAX_PPD || n % 2) {
+            fprintf(stderr, "Invalid Parameters given: ZD_PLT_compute_ppd = %d: an eigenmode table has an even number of points per side in [4, %d]\n",
+                    (int) n, ZD_PLT_MAX_PPD);
+            return 1;
+        }
+    } else if (p->qPLT)
+        ZD_REQUIRE(s->PLT_filename[0] != 0);
     ZD_REQUIRE(p->k_cutoff >= 1);
     if (p->qPLT) ZD_REQUIRE(strncmp(s->ICFormat, "RV", 2) == 0);
     p->f_NL    = s->f_NL;

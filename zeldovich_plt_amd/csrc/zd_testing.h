@@ -49,6 +49,9 @@ void zd_test_poison(int on);
 /* rank >= 0: that rank of the thread-per-GPU driver (zd_generate with ngpu > 1, zd_test_generate_loopback) fails BEFORE its first
  * pass — its peers are then blocked inside their first grouped send / receive, which only an abort ends; -1: nobody */
 void zd_test_fail_rank(int rank);
+/* the PLT dynamical matrix (zd_kernels_plt.hip) at nmodes signed wavenumbers m_xyz[nmodes][3] of a table of n points per side, for the
+ * splitting parameter alpha and `shells` (3, 4 or 5) shells: out6[nmodes][6] = D_xx, D_yy, D_zz, D_xy, D_xz, D_yz */
+int zd_test_plt_matrix(int64_t n, double alpha, int32_t shells, int64_t nmodes, const int32_t *m_xyz, double *out6);
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -278,7 +278,17 @@ int main(int argc, char *argv[]) {
 
     double *eig = nullptr;
     int64_t eig_ppd = 0;
-    if (p.qPLT && zd_load_eigmodes(s.PLT_filename, &eig, &eig_ppd)) exit(1);
+    if (p.qPLT && s.PLT_compute_ppd) {  // the table computed on the GPU (ZD_PLT_compute_ppd) instead of loaded
+        eig_ppd = s.PLT_compute_ppd;
+        fprintf(stderr, "Computing PLT eigenmodes on %lld^3 points.\n", (long long) eig_ppd);
+        eig = (double *) malloc((size_t) eig_ppd * eig_ppd * (eig_ppd / 2 + 1) * 4 * sizeof(double));  // (freed with zd_free, like a loaded one)
+        if (!eig || zd_make_eigenmodes(eig_ppd, eig)) exit(1);
+    } else if (p.qPLT && zd_load_eigmodes(s.PLT_filename, &eig, &eig_ppd))
+        exit(1);
+    char plt_write[1024];  // ZD_PLT_write_filename: the table this run uses, in the layout zd_load_eigmodes reads
+    if (p.qPLT && (zd_param_file_string(argv[1], "ZD_PLT_write_filename", plt_write, sizeof(plt_write)) ||
+                   (plt_write[0] && zd_write_eigmodes(plt_write, eig, eig_ppd))))
+        exit(1);
     if (p.k_cutoff != 1)
         fprintf(stderr, "Using k_cutoff = %f (effective ppd = %d)\n", p.k_cutoff, (int) (p.ppd / p.k_cutoff + .5));
     fprintf(stderr, "Preamble took %f seconds\n", elapsed());
