@@ -85,7 +85,21 @@ typedef struct zd_params {
      * against the earlier header that zero-fills the struct (as every reader here does) runs as before */
     int32_t q2LPT;
     int32_t lpt2_dealias;
-    double lpt2_ratio, lpt2_f2;
+    double lpt2_ratio;
+    /* --- third-order Lagrangian perturbation theory (not in the reference; definition: csrc/zd_kernels_lpt3.hip) ---
+     * q3LPT = 1 (ZD_q3LPT, needs q2LPT = 1): displacement = psi1 + psi2 + psi3, velocity = vnorm psi1 + lpt2_f2 psi2 + lpt3_f3 psi3, with
+     * psi3_j(k) = i k_j P3 / k^2 - lpt3_g3c i (k x C)_j / k^2, P3 the transform of lpt3_g3a det T[D] + lpt3_g3b S3b and C the transverse
+     * source.  The coefficients (ZD_3LPT_D3a, ZD_3LPT_D3b, ZD_3LPT_D3c, ZD_3LPT_f3): 0 = the default, which exists at f_cluster = 1 only:
+     * -1/3, +10/21, +1/7 and 3 vnorm; any other f_cluster needs every enabled term's coefficient and lpt3_f3 given.  lpt3_terms
+     * (ZD_3LPT_terms) leaves terms out: bit 1 = 3a, bit 2 = 3b, bit 4 = 3c, 0 = all (7).  What q2LPT refuses is refused; also
+     * lpt2_dealias = 1 and PPD > 1024 (the third-order round holds ~120 PPD^3 bytes on one GPU; afterwards 40 PPD^3 stay resident).
+     * The six members sit between lpt2_ratio and lpt2_f2: lpt2_f2 stays the LAST member of the struct, as tests/test_lpt2.py pins it, and
+     * every member up to lpt2_ratio keeps its offset.  The struct grows by 40 bytes and lpt2_f2 moves by as much: callers are rebuilt
+     * against this header (a caller that fills the struct by hand zeroes the new members; memset of the struct does). */
+    int32_t q3LPT;
+    int32_t lpt3_terms;
+    double lpt3_g3a, lpt3_g3b, lpt3_g3c, lpt3_f3;
+    double lpt2_f2;
 } zd_params;
 
 /* zd_params.store_mode */

@@ -36,7 +36,10 @@ class ZdParams(C.Structure):
         ("store_mode", C.c_int32), ("serial_z", C.c_int32), ("ngpu", C.c_int32), ("exchange_planes", C.c_int32),
         ("f_NL", C.c_double), ("n_s", C.c_double), ("Omega_M", C.c_double),
         ("version", C.c_int32), ("pass_groups", C.c_int32),
-        ("q2LPT", C.c_int32), ("lpt2_dealias", C.c_int32), ("lpt2_ratio", C.c_double), ("lpt2_f2", C.c_double),
+        ("q2LPT", C.c_int32), ("lpt2_dealias", C.c_int32), ("lpt2_ratio", C.c_double),
+        ("q3LPT", C.c_int32), ("lpt3_terms", C.c_int32), ("lpt3_g3a", C.c_double), ("lpt3_g3b", C.c_double),
+        ("lpt3_g3c", C.c_double), ("lpt3_f3", C.c_double),
+        ("lpt2_f2", C.c_double),  # (stays the last member)
     ]
 
 
@@ -218,11 +221,14 @@ def make_params(ppd, numblock=2, boxsize=720.0, seed=12346, k_cutoff=1.0, qPLT=0
                 PLT_target_z=0.0, z_initial=49.0, f_cluster=1.0, icformat="RVdoubleZel", qdensity=0,
                 qoneslab=-1, qonemode=0, one_mode=(0, 0, 0), corner_modes=0, cpd=None, stream_factor=0,
                 profile=0, f_NL=0.0, n_s=1.0, Omega_M=1.0, store_mode="auto", serial_z=0, ngpu=0, exchange_planes=0,
-                version=2, pass_groups=0, q2LPT=0, lpt2_ratio=0.0, lpt2_f2=0.0, lpt2_dealias=0):
+                version=2, pass_groups=0, q2LPT=0, lpt2_ratio=0.0, lpt2_f2=0.0, lpt2_dealias=0,
+                q3LPT=0, lpt3_g3a=0.0, lpt3_g3b=0.0, lpt3_g3c=0.0, lpt3_f3=0.0, lpt3_terms=0):
     """Parameters with the derived quantities of Parameters::setup (src/parameters.cpp:172-174); version = 1 (legacy
     mt19937 streams) adjusts NumBlock by k_cutoff as the reader does (src/parameters.cpp:129-141).  q2LPT = 1 adds the
     second-order displacements (csrc/zd_kernels_lpt2.hip); lpt2_ratio = D2 / D1^2 and lpt2_f2: 0 = the f_cluster background's;
-    lpt2_dealias = 1 forms its source on the 3 PPD / 2 lattice (Orszag's 3/2 rule, csrc/zd_kernels_lpt2q.hip)."""
+    lpt2_dealias = 1 forms its source on the 3 PPD / 2 lattice (Orszag's 3/2 rule, csrc/zd_kernels_lpt2q.hip).  q3LPT = 1 (with q2LPT = 1) adds
+    the third-order displacements (csrc/zd_kernels_lpt3.hip); lpt3_g3a, lpt3_g3b, lpt3_g3c and lpt3_f3: 0 = the defaults of f_cluster = 1
+    (-1/3, 10/21, 1/7, 3); lpt3_terms leaves terms out (bit 1 = 3a, 2 = 3b, 4 = 3c; 0 = all)."""
     p = ZdParams()
     p.ppd = ppd
     if version == 1 and k_cutoff != 1.0:
@@ -256,6 +262,8 @@ def make_params(ppd, numblock=2, boxsize=720.0, seed=12346, k_cutoff=1.0, qPLT=0
     p.f_NL, p.n_s, p.Omega_M = f_NL, n_s, Omega_M
     p.q2LPT, p.lpt2_ratio, p.lpt2_f2 = q2LPT, lpt2_ratio, lpt2_f2
     p.lpt2_dealias = lpt2_dealias
+    p.q3LPT, p.lpt3_terms = q3LPT, lpt3_terms
+    p.lpt3_g3a, p.lpt3_g3b, p.lpt3_g3c, p.lpt3_f3 = lpt3_g3a, lpt3_g3b, lpt3_g3c, lpt3_f3
     return p
 
 

@@ -406,6 +406,10 @@ static int64_t lpt2_round_bytes(const zd_params *p) {
     const int64_t M = p->lpt2_dealias ? zd::lpt2_dealias_lattice(p->ppd) : p->ppd;
     return M * M * (M + store_row_pad(M)) * 16 + M * M * M * 8;
 }
+// ZD_q3LPT memory: P3(k) and C_x,y,z(k) stay beside S(k), 40 N^3 bytes in all; the third-order round before them peaks at its one-array
+// store + the twelve real Hessian fields + S(k) = 120 N^3 bytes (+ the row pad), of which the four new spectra then take 32 N^3
+static int64_t lpt3_round_bytes(int64_t N) { return N * N * (N + store_row_pad(N)) * 16 + 12 * N * N * N * 8 + lpt2_sk_bytes(N); }
+static int64_t lpt_resident_bytes(const zd_params *p) { return p->q2LPT ? (p->q3LPT ? 5 : 1) * lpt2_sk_bytes(p->ppd) : 0; }
 
 // The two halves of a PLT + density run (zd_route.h plt_dens_split) at the PLT half's stream factor R (<= 0: plan creation's
 // default), and whether their shapes fit together: the PLT half on its field store, the density half density-only with the same
@@ -430,7 +434,8 @@ static int choose_stream_factor_one(const zd_params *p, int nranks, int64_t budg
     // ZA without density: two residues share a pass, so R = 2 is preferred over R = 1 whenever the z FFT is long enough
     const Route r2 = route(p, 2, nranks, zd::ROLE_MAIN);
     if (p->q2LPT && lpt2_round_bytes(p) > budget_bytes) return -1;
-    const int64_t lpt2_resident = p->q2LPT ? lpt2_sk_bytes(N) : 0;
+    if (p->q3LPT && lpt3_round_bytes(N) > budget_bytes) return -1;
+    const int64_t lpt2_resident = lpt_resident_bytes(p);  // (S(k); with the third order also P3(k), C_x,y,z(k))
     for (int R = r2.legal && r2.pstep == 2 ? 2 : 1; N / R >= zd::min_zlen(own); R = zd::next_factor(own, R)) {
         const Route rt = route(p, R, nranks, zd::ROLE_MAIN);
         if (!rt.legal || rt.family != own) continue;
@@ -495,6 +500,7 @@ int zd_choose_pass_groups(const zd_params *p_in, int ngpu, int64_t budget_bytes,
     if (ngpu < 1) ngpu = 1;
     const char *why = zd::lpt2_refusal(p, ngpu);  // (pass groups included: every GPU would run the second-order round)
     if (!why) why = zd::lpt2_dealias_refusal(p);
+    if (!why) why = zd::lpt3_refusal(p);
     if (why) {
         fprintf(stderr, "zeldovich_hip: %s\n", why);
         return 1;
@@ -760,6 +766,63 @@ static int make_lpt2_source(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d
     d_sk = std::move(d_out);
     return 0;
 }
+// ZD_q3LPT: the third-order round (definition and shape: zd_kernels_lpt3.hip), run once after the second-order round with its S(k) in
+// d_sk; d_out[0 .. 3] = P3(k), C_x(k), C_y(k), C_z(k) in the layout of S(k), already scaled by N^-3 (handed to the caller).  Six pair
+// passes over one one-array store — generator, z and y stages of a plan of the second-order round's kind, then the x lines into two
+// real fields each —, the pointwise sources over four of the twelve fields, and four runs of the f_NL phi round's forward chain.  The
+// eight fields that are no longer needed are freed before the four spectra are allocated: the peak is lpt3_round_bytes.
+static int make_lpt3_sources(const zd_params *p, const zd_pk *pk, const cplx *d_sk, DevBuf<cplx> (&d_out)[4]) {
+    const int64_t N = p->ppd, n3 = N * N * N;
+    zd_params pp     = *p;
+    pp.stream_factor = 1;   // the forward z transform needs every plane of a row
+    pp.qoneslab      = -1;  // (the sources need the whole field whatever is delivered)
+    PlanPtr plan;
+    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 2, nullptr, plan)) return 1;
+    zd_plan *ph = plan.get();
+    auto no_room = [&]() {
+        fprintf(stderr, "zeldovich_hip: ZD_q3LPT needs %.1f GB of HBM for the third-order round at PPD %lld\n", lpt3_round_bytes(N) / 1e9,
+                (long long) N);
+        return 1;
+    };
+    DevBuf<cplx> d_pair, d_spec[4];  // d_spec: handed to the caller at the end: every early return frees them
+    DevBuf<double> d_td[6], d_ts[6];
+    zd::Lpt3Fields F;
+    if (d_pair.store_alloc((size_t) zd_plan_exchange_bytes(ph) / sizeof(cplx)) != hipSuccess) return no_room();
+    for (int f = 0; f < 6; f++) {
+        if (d_td[f].store_alloc((size_t) n3) != hipSuccess || d_ts[f].store_alloc((size_t) n3) != hipSuccess) return no_room();
+        F.d[f] = d_td[f];
+        F.s[f] = d_ts[f];
+    }
+    ph->g.lpt2_sk = d_sk;
+    for (int pass = 1; pass <= 6; pass++) {
+        ph->g.lpt3 = pass;
+        if (zd_plan_stage_z(ph, 0, d_pair, 0) || zd_plan_stage_y(ph, d_pair, 0)) return 1;
+        if (zd::launch_lpt3_xpair(ph->S, ph->d_twN, d_pair, d_td[pass - 1], d_ts[pass - 1], (int) N, 0)) return 1;
+    }
+    if (zd::launch_lpt3_point(F, zd::lpt3_g3a(p), zd::lpt3_g3b(p), n3, 0)) return 1;
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    for (int f = 0; f < 6; f++) {
+        d_ts[f].reset();
+        if (f >= 4) d_td[f].reset();
+    }
+    int lN = 0;
+    while ((1 << lN) < (int) N) lN++;
+    for (int f = 0; f < 4; f++) {
+        if (d_spec[f].store_alloc((size_t) lpt2_sk_bytes(N) / sizeof(cplx)) != hipSuccess) return no_room();
+        if (zd::launch_lpt3_xfwd(ph->S, ph->d_twN, d_td[f], d_pair, (int) N, 0)) return 1;
+        if (zd::launch_fnl_stage(1, ph->S, 0.0, ph->d_twN, d_pair, nullptr, (int) N, lN, 0)) return 1;
+        if (zd::launch_fnl_stage(2, ph->S, 0.0, ph->d_twN, d_pair, d_spec[f], (int) N, lN, 0)) return 1;
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    for (int f = 0; f < 4; f++) d_out[f] = std::move(d_spec[f]);
+    return 0;
+}
+// a plan of the final pass takes the four spectra over and points its generator at them
+static void adopt_lpt3(zd_plan *pl, DevBuf<cplx> (&d_spec)[4]) {
+    for (int f = 0; f < 4; f++) pl->d_lpt3_owned[f] = std::move(d_spec[f]);
+    pl->g.lpt3_p3 = pl->d_lpt3_owned[0];
+    for (int j = 0; j < 3; j++) pl->g.lpt3_c[j] = pl->d_lpt3_owned[1 + j];
+}
 // a ZD_q2LPT job the route takes for this call (the refusal printed otherwise), asked BEFORE the second-order round is run
 static int lpt2_route_check(const zd_params *p, int nranks, int rank) {
     const zd_params pc = zd::canonical(p);
@@ -834,8 +897,10 @@ int zd_plan_create(const zd_params *p, const zd_pk *pk, const double *eig, int64
                    zd_plan **out) {
     PlanPtr pl;
     DevBuf<cplx> d_phik;  // PhiK or S(k): the round runs here, once; the plan owns the result and its Z stages read it beside their draws
-    if (p->q2LPT) {
+    DevBuf<cplx> d_lpt3[4];  // ZD_q3LPT: P3(k), C_x,y,z(k) of the third-order round, likewise
+    if (p->q2LPT || p->q3LPT) {
         if (lpt2_route_check(p, nranks, rank) || make_lpt2_source(p, pk, d_phik)) return 1;
+        if (p->q3LPT && make_lpt3_sources(p, pk, d_phik, d_lpt3)) return 1;
     } else if (p->f_NL != 0.) {  // the phi round; the Z stages read D = PhiK * M
         if (nranks != 1) {
             fprintf(stderr, "zeldovich_hip: ZD_f_NL != 0 runs on one rank (the forward z transform of the phi field needs every plane)\n");
@@ -846,6 +911,7 @@ int zd_plan_create(const zd_params *p, const zd_pk *pk, const double *eig, int64
     }
     if (plan_create_ex(p, pk, eig, eig_ppd, rank, nranks, 0, d_phik, pl)) return 1;
     pl->d_phik_owned = std::move(d_phik);
+    if (p->q3LPT) adopt_lpt3(pl.get(), d_lpt3);
     *out             = pl.release();
     return 0;
 }
@@ -896,7 +962,8 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
             zdpcg::make_bit_table(b);
             return b;
         }();
-        if (zdk_upload_bit_table(&bt) != 0 || zdk_upload_bit_table_fz(&bt) != 0 || zdk_upload_bit_table_lpt2(&bt) != 0) {
+        if (zdk_upload_bit_table(&bt) != 0 || zdk_upload_bit_table_fz(&bt) != 0 || zdk_upload_bit_table_lpt2(&bt) != 0
+            || zdk_upload_bit_table_lpt3(&bt) != 0) {
             fprintf(stderr, "zeldovich_hip: uploading the RNG jump table failed\n");
             return 1;
         }
@@ -1395,6 +1462,11 @@ static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk,
         g.lpt2_gamma = -zd::lpt2_ratio(p);
         g.lpt2_alpha = zd::lpt2_alpha(p);
         g.lpt2_f2g   = zd::lpt2_f2(p) * g.lpt2_gamma;
+        if (p->q3LPT) {  // ... plus the third order (the spectra: adopt_lpt3)
+            g.lpt3     = 7;
+            g.lpt3_g3c = zd::lpt3_g3c(p);
+            g.lpt3_f3  = zd::lpt3_f3(p);
+        }
     }
     if (role == zd::ROLE_PHI) g.qPLT = 0;  // the phi pass stops before the displacement algebra (zeldovich.cpp:385-391)
     plan_zstage_jobs(pl);
@@ -1865,7 +1937,7 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
                 void *user, zd_stats *out) {
     // ZD_NumGPU: one host thread per GPU, exchange inside the library (zd_multi.cpp).  (ZD_qoneslab finishes ONE plane of one
     // pass and reports the reductions of that slab alone, output.cpp:197: that is this single-GPU path's job.)
-    if ((p_in->q2LPT || p_in->lpt2_dealias) && lpt2_route_check(p_in, p_in->ngpu > 1 ? p_in->ngpu : 1, 0)) return 1;
+    if ((p_in->q2LPT || p_in->lpt2_dealias || p_in->q3LPT) && lpt2_route_check(p_in, p_in->ngpu > 1 ? p_in->ngpu : 1, 0)) return 1;
     if (p_in->ngpu > 1 && p_in->qoneslab < 0) {
         int ndev = 0;
         HIPCHECK(hipGetDeviceCount(&ndev));
@@ -1903,10 +1975,14 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
     }
     // ---- ZD_q2LPT: the second-order round (zd_kernels_lpt2.hip); the chooser has counted S(k) beside the passes' stores ----
     if (p.q2LPT && make_lpt2_source(&p, pk, d_phik)) return 1;
+    // ---- ZD_q3LPT: the third-order round (zd_kernels_lpt3.hip); P3(k) and C_x,y,z(k) stay beside S(k), counted likewise ----
+    DevBuf<cplx> d_lpt3[4];
+    if (p.q3LPT && make_lpt3_sources(&p, pk, d_phik, d_lpt3)) return 1;
     PlanPtr plan;
     if (plan_create_ex(&p, pk, eig, eig_ppd, 0, 1, 0, d_phik, plan)) return 1;
     zd_plan *pl      = plan.get();
     pl->d_phik_owned = std::move(d_phik);
+    if (p.q3LPT) adopt_lpt3(pl, d_lpt3);
     const int R = pl->R, recsize = pl->ec.recsize, npass = pl->npass, pstep = pl->pstep;
     const int64_t Pp = zd_plan_local_planes(pl);  // planes delivered per pass
     const bool want_rec = pl->narray >= 2 && !pl->dens_only, want_dens = p.qdensity != 0;

@@ -70,6 +70,18 @@ struct GenConst {
     int lpt2;
     const zdfft::cplx *lpt2_sk;
     double lpt2_gamma, lpt2_alpha, lpt2_f2g;
+    // third-order displacements (zd_kernels_lpt3.hip).  lpt3 = 1 .. 6: the Hessian pair pass of that number of the third-order round
+    // (the plan's one array holds T_ab[D] + i T_ab[S]; S(k) in lpt2_sk); 7: the final pass, which reads P3(k) and C_x,y,z(k) (the
+    // layout of lpt2_sk) beside S(k) and its own draws — the lpt2 members hold what they hold for the second order's final pass;
+    // 0 everywhere else
+    int lpt3;
+    const zdfft::cplx *lpt3_p3, *lpt3_c[3];
+    double lpt3_g3c, lpt3_f3;
+};
+
+// the twelve real N^3 Hessian fields of the third-order round, order xx, yy, zz, xy, xz, yz (k_lpt3_point, zd_kernels_lpt3.hip)
+struct Lpt3Fields {
+    double *d[6], *s[6];  // T_ab[D], T_ab[S]
 };
 
 // ZD_Version = 1: one mt19937 stream per yres (src/power_spectrum.cpp:18-25) between two launches of k_v1_draw: the state

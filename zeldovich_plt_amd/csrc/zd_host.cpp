@@ -667,6 +667,14 @@ int zd_params_from_file(const char *path, zd_params *p, zd_param_strings *s) {
     D("ZD_2LPT_D2", p->lpt2_ratio);
     D("ZD_2LPT_f2", p->lpt2_f2);
     I("ZD_2LPT_dealias", p->lpt2_dealias);  // the source on the 3 PPD / 2 lattice (csrc/zd_kernels_lpt2q.hip)
+    // third-order displacements on top of ZD_q2LPT (csrc/zd_kernels_lpt3.hip): 0 for a coefficient = its default at ZD_f_cluster = 1;
+    // ZD_3LPT_terms leaves terms out (bit 1 = 3a, 2 = 3b, 4 = 3c; 0 = all)
+    I("ZD_q3LPT", p->q3LPT);
+    D("ZD_3LPT_D3a", p->lpt3_g3a);
+    D("ZD_3LPT_D3b", p->lpt3_g3b);
+    D("ZD_3LPT_D3c", p->lpt3_g3c);
+    D("ZD_3LPT_f3", p->lpt3_f3);
+    I("ZD_3LPT_terms", p->lpt3_terms);
     // the run checks itself: records at n sites against the direct summation over the modes (csrc/zd_kernels_ds.hip)
     I("ZD_SelfCheck", s->SelfCheck);
     D("ZD_SelfCheck_tol", s->SelfCheck_tol);

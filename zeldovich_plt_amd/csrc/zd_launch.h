@@ -141,6 +141,16 @@ int launch_lpt2q_xsrc(int m, const void *tw, int pass, void *data, long long pit
 // the last z lines of the store [z][y][x] (row pitch `pitch`): columns |kx| < n/2, rows 0 <= ky < n/2, outputs |kz| < n/2, conjugated,
 // into sk[ky][kz][x] of the n layout (zeros on its Nyquist planes)
 int launch_lpt2q_zsrc(int m, int n, const void *tw, const void *store, long long pitch, void *sk, hipStream_t st);
+// ---- third-order displacements (zd_kernels_lpt3.hip) ----
+// the generator of a plan with GenConst::lpt3 != 0 (launch_gen hands such plans over): Hessian pairs or the final pass
+int launch_gen_lpt3(const GenConst &g, const GenJumps &J, const JobList &jobs, const StoreLayout &S, int ky0, int nky, int L, int residue,
+                    const void *twN, void *Y, hipStream_t st);
+// x lines of the planes [0, nplanes) of a one-array store in a pair pass: inverse transform, Re -> td[z][y][x], Im -> ts[z][y][x]
+int launch_lpt3_xpair(const StoreLayout &S, const void *tw, const void *data, double *td, double *ts, int nplanes, hipStream_t st);
+// the sources of the third order at `nsites` lattice sites, written over F.d[0 .. 3]: g3a S3a + g3b S3b, C_x, C_y, C_z
+int launch_lpt3_point(const Lpt3Fields &F, double g3a, double g3b, long long nsites, hipStream_t st);
+// rows of the real field src[z][y][x] / N^3 through the forward x transform into the one-array store (launch_fnl_stage 1, 2 go on)
+int launch_lpt3_xfwd(const StoreLayout &S, const void *tw, const double *src, void *data, int nplanes, hipStream_t st);
 // ---- ZD_Version = 1 streams (zd_kernels_v1.hip) ----
 int launch_v1_seed(unsigned long long seed, int block, V1Stream *streams, hipStream_t st);
 int launch_v1_draw(const GenConst &g, int block, int ky0, int ky_stride, int nrows, V1Stream *streams, void *dev, int *err,
@@ -152,3 +162,4 @@ int launch_copy16(const void *in, void *out, long long n16, hipStream_t st);
 extern "C" int zdk_upload_bit_table(const zdpcg::BitTable *host);
 extern "C" int zdk_upload_bit_table_fz(const zdpcg::BitTable *host);
 extern "C" int zdk_upload_bit_table_lpt2(const zdpcg::BitTable *host);
+extern "C" int zdk_upload_bit_table_lpt3(const zdpcg::BitTable *host);

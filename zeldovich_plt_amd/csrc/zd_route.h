@@ -124,6 +124,31 @@ inline double lpt2_alpha(const zd_params *p) { return (sqrt(1. + 24 * p->f_clust
 inline double lpt2_ratio(const zd_params *p) { return p->lpt2_ratio != 0. ? p->lpt2_ratio : -(2 * lpt2_alpha(p) + 1) / (6 * lpt2_alpha(p) + 1); }
 inline double lpt2_f2(const zd_params *p) { return p->lpt2_f2 != 0. ? p->lpt2_f2 : 2 * lpt2_alpha(p); }
 
+// Third-order displacements (zd_params.q3LPT; definition in zd_kernels_lpt3.hip) ride on the second order: whatever lpt2_refusal refuses
+// is refused before this is asked.  The cubic term of a de-aliased round would need the lattice of 2 PPD points per side; the round
+// holds twelve real fields beside its store and S(k), 120 PPD^3 bytes; the default coefficients are those of the f_cluster = 1
+// background.  NULL: accepted.
+inline bool lpt3_term(const zd_params *p, int bit) { return ((p->lpt3_terms ? p->lpt3_terms : 7) & bit) != 0; }
+inline const char *lpt3_refusal(const zd_params *p) {
+    if (!p->q3LPT) return nullptr;
+    if (p->q3LPT != 1) return "ZD_q3LPT must be 0 or 1";
+    if (p->q2LPT != 1) return "ZD_q3LPT = 1 needs ZD_q2LPT = 1";
+    if (p->lpt3_terms < 0 || p->lpt3_terms > 7) return "ZD_q3LPT = 1 takes ZD_3LPT_terms in 0 ... 7 (bit 1 = 3a, bit 2 = 3b, bit 4 = 3c)";
+    if (p->lpt2_dealias) return "ZD_q3LPT = 1 is not supported together with ZD_2LPT_dealias = 1 (its cubic term would need the lattice of 2 PPD)";
+    if (p->ppd > 1024) return "ZD_q3LPT = 1 needs PPD <= 1024 (the third-order round holds 120 PPD^3 bytes on one GPU)";
+    if (p->f_cluster != 1.
+        && ((lpt3_term(p, 1) && p->lpt3_g3a == 0.) || (lpt3_term(p, 2) && p->lpt3_g3b == 0.) || (lpt3_term(p, 4) && p->lpt3_g3c == 0.)
+            || p->lpt3_f3 == 0.))
+        return "ZD_q3LPT = 1 with ZD_f_cluster != 1 needs ZD_3LPT_f3 and the coefficient of every enabled term given (the defaults are "
+               "those of f_cluster = 1)";
+    return nullptr;
+}
+// its coefficients as the kernels take them: 0 for a term that is left out, else the given value or the default
+inline double lpt3_g3a(const zd_params *p) { return !lpt3_term(p, 1) ? 0. : p->lpt3_g3a != 0. ? p->lpt3_g3a : -1. / 3.; }
+inline double lpt3_g3b(const zd_params *p) { return !lpt3_term(p, 2) ? 0. : p->lpt3_g3b != 0. ? p->lpt3_g3b : 10. / 21.; }
+inline double lpt3_g3c(const zd_params *p) { return !lpt3_term(p, 4) ? 0. : p->lpt3_g3c != 0. ? p->lpt3_g3c : 1. / 7.; }
+inline double lpt3_f3(const zd_params *p) { return p->lpt3_f3 != 0. ? p->lpt3_f3 : 3 * lpt2_alpha(p); }
+
 // reference arrays of a job: density only one (zeldovich.cpp:871-876), PLT — and the second order's own velocity field — four, else two
 inline int ref_arrays(const zd_params *p) { return p->qdensity == 2 ? 1 : ((p->qPLT || p->q2LPT) ? 4 : 2); }
 
@@ -204,6 +229,7 @@ inline Route route(const zd_params *p, int R_given, int nranks, int role, int ra
     if (!grad) {
         if (const char *why = lpt2_refusal(p, nranks)) r.refuse(true, "%s", why);
         if (const char *why = lpt2_dealias_refusal(p)) r.refuse(true, "%s", why);
+        if (const char *why = lpt3_refusal(p)) r.refuse(true, "%s", why);
     }
     bool comp = false;
     if (!pow2) {
