@@ -370,6 +370,26 @@ int zd_plan_direct_sum(zd_plan *plan, int64_t nsites, const int64_t *sites_zyx, 
 int zd_direct_sum(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int64_t nsites, const int64_t *sites_zyx,
                   double *out7);
 
+/* ---- ZD_q2LPT / ZD_q3LPT plans: direct summation and band power of the three orders ------------
+ * An LPT plan keeps the spectra of its higher orders resident (S(k); with ZD_q3LPT also P3(k) and C_x,y,z(k)), and a delivered record
+ * is the unnormalised inverse transform of amplitudes that are linear in them; the definition is pinned in
+ * csrc/zd_kernels_lpt_ds.hip.  The sums pin the final pass of an LPT run — generator, z, y, x stages, epilogue, any stream factor —
+ * and take the spectra as the plan holds them: they do not check the second- and third-order rounds.
+ * (A ZD_qonemode plan is a single plane wave, which has no higher order: orders 2 and 3 are zero there, exactly.)
+ *   zd_plan_lpt_direct_sum   sites_zyx as for zd_plan_direct_sum; out18: HOST array of nsites x 3 orders x (qx, qy, qz, vx, vy, vz):
+ *                            order 1 (the ZA field, velocities alpha q), order 2, order 3 (zero without ZD_q3LPT).  The delivered
+ *                            record is the sum over the orders.  Two calls on one plan return the same bits.
+ *   zd_plan_lpt_power        bins and counting of zd_plan_measure_power; sums8: HOST array of nbins x (sum_k, sum_input, sum_dens,
+ *                            sum_disp1, sum_disp2, sum_disp3, sum_disp, sum_vel): the displacement power of each order alone, then of
+ *                            the delivered displacement and velocity (the sums over the orders, cross terms included).
+ * zd_lpt_direct_sum and zd_lpt_power are the one-call forms: they create the plan, rounds included.  Refused (message, non-zero), before
+ * a plan or the GPU is touched where possible: parameters without ZD_q2LPT = 1, whatever a ZD_q2LPT / ZD_2LPT_dealias / ZD_q3LPT plan
+ * refuses, nsites < 1 or > 64, a site outside the lattice, bin_width < 1, nbins < zd_power_nbins, NULL arrays. */
+int zd_plan_lpt_direct_sum(zd_plan *plan, int64_t nsites, const int64_t *sites_zyx, double *out18, void *hip_stream);
+int zd_lpt_direct_sum(const zd_params *p, const zd_pk *pk, int64_t nsites, const int64_t *sites_zyx, double *out18);
+int zd_plan_lpt_power(zd_plan *plan, int32_t bin_width, int64_t nbins, int64_t *count, double *sums8, void *hip_stream);
+int zd_lpt_power(const zd_params *p, const zd_pk *pk, int32_t bin_width, int64_t nbins, int64_t *count, double *sums8);
+
 /* ---- diagnostics ------------------------------------------------------------------------------
  * Which kernel variants this process has launched so far, and how often: one line "count<TAB>line<TAB>launcher" per launch
  * site of the library, the launcher named with its template arguments (transform length, elements per thread, tile shape,

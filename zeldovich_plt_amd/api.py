@@ -89,6 +89,7 @@ EXPORTED_SYMBOLS = [
     "zd_pk_sigmaR", "zd_pk_destroy", "zd_load_eigmodes", "zd_free", "zd_comm_abort", "zd_comm_traffic", "zd_choose_pass_groups", "zd_plan_run_passes", "zd_comm_probe", "zd_choose_pass_groups_measured",
     "zd_dispatch_report", "zd_power_nbins", "zd_plan_measure_power", "zd_measure_power",
     "zd_plan_direct_sum", "zd_direct_sum", "zd_make_eigenmodes", "zd_write_eigmodes", "zd_param_file_string",
+    "zd_plan_lpt_direct_sum", "zd_lpt_direct_sum", "zd_plan_lpt_power", "zd_lpt_power",
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
@@ -198,6 +199,10 @@ def _load(path, testing):
     L.zd_measure_power.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i64, vp, vp, vp, vp, vp, vp]
     L.zd_plan_direct_sum.argtypes = [vp, i64, vp, vp, vp]
     L.zd_direct_sum.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i64, vp, vp]
+    L.zd_plan_lpt_direct_sum.argtypes = [vp, i64, vp, vp, vp]
+    L.zd_lpt_direct_sum.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), i64, vp, vp]
+    L.zd_plan_lpt_power.argtypes = [vp, i32, i64, vp, vp, vp]
+    L.zd_lpt_power.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), i32, i64, vp, vp]
     L.zd_dispatch_report.argtypes = [C.c_char_p, i64]
     L.zd_dispatch_report.restype = i64
     return L
@@ -500,6 +505,46 @@ def direct_sum(params, ps, sites, eig=None):
     return out
 
 
+def lpt_direct_sum(params, ps, sites):
+    """The three orders of a ZD_q2LPT / ZD_q3LPT run at the lattice sites [(z, y, x), ...], by direct summation over the first-order
+    modes and the plan's resident higher-order spectra (zd_lpt_direct_sum; definition in csrc/zd_kernels_lpt_ds.hip).  Returns float64
+    [nsites, 3, 6] = order 1, 2, 3 x (qx, qy, qz, vx, vy, vz); the delivered record is the sum over the orders."""
+    s = _site_array(sites, params.ppd)
+    out = np.zeros((s.shape[0], 3, 6), dtype=np.float64)
+    if load_library().zd_lpt_direct_sum(C.byref(params), C.byref(ps.pk), s.shape[0], s.ctypes.data, out.ctypes.data):
+        raise RuntimeError("zd_lpt_direct_sum failed; see stderr")
+    return out
+
+
+LPT_POWER_SUMS = ("sum_k", "sum_input", "sum_dens", "sum_disp1", "sum_disp2", "sum_disp3", "sum_disp", "sum_vel")
+
+
+def _lpt_power_arrays(ppd, bin_width):
+    nb = power_nbins(ppd, bin_width)
+    if nb <= 0:
+        raise ValueError("lpt_power: bin_width must be an integer >= 1")
+    return nb, np.zeros(nb, dtype=np.int64), np.zeros((nb, len(LPT_POWER_SUMS)), dtype=np.float64)
+
+
+def _lpt_power_dict(count, sums):
+    out = {"count": count}
+    for j, name in enumerate(LPT_POWER_SUMS):
+        out[name] = np.ascontiguousarray(sums[:, j])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["k_mean"] = np.where(count > 0, out["sum_k"] / count, np.nan)
+    return out
+
+
+def lpt_power(params, ps, bin_width=1):
+    """Band power of a ZD_q2LPT / ZD_q3LPT run (zd_lpt_power; definition in csrc/zd_kernels_lpt_ds.hip): a dict of numpy arrays over
+    the integer |k| shells of width bin_width: count, sum_k, sum_input, sum_dens, the displacement power of each order sum_disp1,
+    sum_disp2, sum_disp3, of the delivered displacement sum_disp and velocity sum_vel, and the derived k_mean."""
+    nb, count, sums = _lpt_power_arrays(params.ppd, bin_width)
+    if load_library().zd_lpt_power(C.byref(params), C.byref(ps.pk), int(bin_width), nb, count.ctypes.data, sums.ctypes.data):
+        raise RuntimeError("zd_lpt_power failed; see stderr")
+    return _lpt_power_dict(count, sums)
+
+
 def generate_planes(params, ps, on_plane, eig=None):
     """zd_generate with a per-plane consumer: on_plane(z, records[y, x]) sees a VIEW valid only during the call (like the
     reference's single output buffer); nothing is accumulated here.  Returns the statistics + the number of planes."""
@@ -601,6 +646,21 @@ class Plan:
         if self.L.zd_plan_direct_sum(self.h, s.shape[0], s.ctypes.data, out.ctypes.data, stream):
             raise RuntimeError("zd_plan_direct_sum failed; see stderr")
         return out
+
+    def lpt_direct_sum(self, sites, stream=0):
+        """the three orders of this ZD_q2LPT / ZD_q3LPT plan at the sites (zd_plan_lpt_direct_sum): [nsites, 3, 6]"""
+        s = _site_array(sites, self.params.ppd)
+        out = np.zeros((s.shape[0], 3, 6), dtype=np.float64)
+        if self.L.zd_plan_lpt_direct_sum(self.h, s.shape[0], s.ctypes.data, out.ctypes.data, stream):
+            raise RuntimeError("zd_plan_lpt_direct_sum failed; see stderr")
+        return out
+
+    def lpt_power(self, bin_width=1, stream=0):
+        """band power of the three orders of this ZD_q2LPT / ZD_q3LPT plan (zd_plan_lpt_power)"""
+        nb, count, sums = _lpt_power_arrays(self.params.ppd, bin_width)
+        if self.L.zd_plan_lpt_power(self.h, int(bin_width), nb, count.ctypes.data, sums.ctypes.data, stream):
+            raise RuntimeError("zd_plan_lpt_power failed; see stderr")
+        return _lpt_power_dict(count, sums)
 
     def stats(self):
         st = ZdStats()

@@ -19,6 +19,9 @@
 //          delivered fields are then not transforms of Hermitian fields), ZD_Version = 1, whose draws are sequential, and ZD_q2LPT
 //          plans, whose delivered fields hold a second-order part the sweep does not regenerate; a site outside [0, N)^3, fewer
 //          than 1 or more than 64 sites, NULL arrays.
+//          (A ZD_q2LPT / ZD_q3LPT plan has entry points of its own, zd_plan_lpt_direct_sum / zd_lpt_direct_sum in zd_kernels_lpt_ds.hip: its
+//          first order is this sweep, run through ds_sweep_sites with the velocity factor lpt2_alpha, its higher orders are summed from
+//          the spectra the plan keeps.)
 //
 //   ZD_f_NL plans.  The second pass of the reference forms D = PhiK M for every mode but k = 0 (src/zeldovich.cpp:393-400: no zero
 //          rule), and so do k_gen and this sweep; the row ky = N/2 stays unread, as in the y stage.  Modes on the planes |kx| = N/2,
@@ -42,6 +45,8 @@
 //   Sums.  thread -> wave (shuffles, fixed order) -> workgroup (LDS, wave 0..3 in order) -> one partial per workgroup in a
 //          buffer; k_ds_reduce adds the partials of a launch group in a fixed order.  No floating-point atomics: two calls on one
 //          plan return the same bits.
+// Shared with zd_kernels_lpt_ds.hip through zd_sweep.h: the sites of a launch group (DsSites, make_ds_sites), k_ds_reduce's launcher
+// (any number of sums per site) and ds_sweep_sites, the launches of zd_plan_direct_sum behind its refusals.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -60,21 +65,16 @@ using zdfft::cplx;
 using namespace zdgen;
 using zdsweep::SweepJumps;
 using zdsweep::SweepMode;
+using zdsweep::DsSites;
+using zdsweep::DS_BX;
+using zdsweep::DS_NS;
+using zdsweep::DS_RESEED;
+using zdsweep::DS_MAX_SITES;
 
 namespace {
 
-constexpr int DS_BX = 256;        // threads (consecutive x) per workgroup; a thread walks every z of its row
-constexpr int DS_NS = 8;          // sites per launch
 constexpr int DS_NQ = 7;          // qx, qy, qz, vx, vy, vz, density
-constexpr int DS_RESEED = 32;     // FAST rows: z steps between two table look-ups of a site's phase
-constexpr int DS_MAX_SITES = 64;
 constexpr int DS_RB = 256;        // threads of k_ds_reduce
-
-template <int NS>
-struct DsSites {
-    int z[NS], y[NS], x[NS];
-    double wr[NS], wi[NS];  // e^{2 pi i z_s / N}: the rotation of the site's phase per z step
-};
 
 template <bool PLT, bool PLAW, bool FAST, int NS>
 __global__ __launch_bounds__(DS_BX) void k_ds_sweep(GenConst g, SweepJumps J, DsSites<NS> S, int ky_first, int ky_stride, int lG, double vnorm,
@@ -247,12 +247,6 @@ int launch_ds(const GenConst &g, const SweepJumps &J, const DsSites<DS_NS> &S, i
     return 1;
 }
 
-int launch_ds_reduce(const double *partial, long long nwg, double *out, hipStream_t st) {
-    hipLaunchKernelGGL(k_ds_reduce, dim3(DS_NS * DS_NQ), dim3(DS_RB), 0, st, partial, nwg, DS_NS * DS_NQ, out);
-    ZD_LAUNCH_CHECK();
-    return 0;
-}
-
 // what both entry points refuse before a plan or the GPU is touched; NULL: nothing
 const char *ds_refusal(const zd_params &p, int64_t nsites, const int64_t *sites, double *out7, char *buf, size_t cap) {
     if (!sites || !out7) return "zd_plan_direct_sum needs a site array and an output array";
@@ -273,6 +267,64 @@ const char *ds_refusal(const zd_params &p, int64_t nsites, const int64_t *sites,
 }
 
 }  // namespace
+
+namespace zdsweep {
+
+int launch_ds_reduce(const double *partial, long long nwg, int nv, double *out, hipStream_t st) {
+    hipLaunchKernelGGL(k_ds_reduce, dim3(nv), dim3(DS_RB), 0, st, partial, nwg, nv, out);
+    ZD_LAUNCH_CHECK();
+    return 0;
+}
+
+DsSites<DS_NS> make_ds_sites(int N, int64_t nsites, const int64_t *sites_zyx, int grp) {
+    const long double TWO_PI = 2.0L * 3.14159265358979323846264338327950288L;
+    DsSites<DS_NS> S;
+    for (int s = 0; s < DS_NS; s++) {  // a short last group sums its first site again; those sums are dropped
+        const int64_t i = (int64_t) grp * DS_NS + s < nsites ? (int64_t) grp * DS_NS + s : (int64_t) grp * DS_NS;
+        S.z[s] = (int) sites_zyx[3 * i], S.y[s] = (int) sites_zyx[3 * i + 1], S.x[s] = (int) sites_zyx[3 * i + 2];
+        const long double a = TWO_PI * (long double) S.z[s] / (long double) N;
+        S.wr[s] = (double) cosl(a), S.wi[s] = (double) sinl(a);
+    }
+    return S;
+}
+
+int ds_sweep_sites(zd_plan *pl, int64_t nsites, const int64_t *sites_zyx, double vnorm, double *out7, hipStream_t st) {
+    const GenConst &g = pl->g;
+    const int N = pl->N, G = pl->nranks, rank = pl->rank, Hq = pl->Hq;  // rows ky = rank + G i, i < Hq
+    constexpr int NV = DS_NS * DS_NQ;
+    const int ngroups = (int) ((nsites + DS_NS - 1) / DS_NS);
+    const long long nwg = (long long) ((N + DS_BX - 1) / DS_BX) * Hq;  // workgroups = partials of a launch group
+    zdown::DevBuf<double> part, sums;
+    if (part.alloc(NV * (size_t) nwg) != hipSuccess || sums.alloc((size_t) NV * ngroups) != hipSuccess) {
+        fprintf(stderr, "zeldovich_hip: direct summation: no device memory for %lld partial sums\n", nwg * NV);
+        return 1;
+    }
+    const SweepJumps J = zdsweep::make_sweep_jumps(N);
+    const bool fast = g.genf_tab && !g.phik && !g.qonemode;
+    for (int grp = 0; grp < ngroups; grp++) {
+        const DsSites<DS_NS> S = make_ds_sites(N, nsites, sites_zyx, grp);
+        double *partial = part;
+        const size_t per_row = (size_t) ((N + DS_BX - 1) / DS_BX) * NV;
+        int rc = 0;
+        if (fast) {  // the plane ky = 0 (rank 0) through the general form, every other row through the table arithmetic
+            const int skip = rank == 0 ? 1 : 0;
+            if (skip) rc = launch_ds<false>(g, J, S, 0, G, 1, pl->S.lG, vnorm, pl->d_twN, partial, st);
+            if (!rc) rc = launch_ds<true>(g, J, S, rank + skip * G, G, Hq - skip, pl->S.lG, vnorm, pl->d_twN, partial + skip * per_row, st);
+        } else {
+            rc = launch_ds<false>(g, J, S, rank, G, Hq, pl->S.lG, vnorm, pl->d_twN, partial, st);
+        }
+        if (rc || launch_ds_reduce(partial, nwg, NV, sums + (size_t) grp * NV, st)) return 1;
+    }
+    std::vector<double> h((size_t) NV * ngroups);
+    if (hipMemcpyAsync(h.data(), sums, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        fprintf(stderr, "zeldovich_hip: direct summation failed: %s\n", hipGetErrorString(hipGetLastError()));
+        return 1;
+    }
+    std::copy(h.begin(), h.begin() + DS_NQ * nsites, out7);  // [group][site of the group][7] = [site][7]
+    return 0;
+}
+
+}  // namespace zdsweep
 
 extern "C" int zd_plan_direct_sum(zd_plan *pl, int64_t nsites, const int64_t *sites_zyx, double *out7, void *hip_stream) {
     if (!pl) {
@@ -295,46 +347,7 @@ extern "C" int zd_plan_direct_sum(zd_plan *pl, int64_t nsites, const int64_t *si
         fprintf(stderr, "zeldovich_hip: this plan does not generate the modes of a run (no direct summation)\n");
         return 1;
     }
-    hipStream_t st = (hipStream_t) hip_stream;
-    const int N = pl->N, G = pl->nranks, rank = pl->rank, Hq = pl->Hq;  // rows ky = rank + G i, i < Hq
-    constexpr int NV = DS_NS * DS_NQ;
-    const int ngroups = (int) ((nsites + DS_NS - 1) / DS_NS);
-    const long long nwg = (long long) ((N + DS_BX - 1) / DS_BX) * Hq;  // workgroups = partials of a launch group
-    zdown::DevBuf<double> part, sums;
-    if (part.alloc(NV * (size_t) nwg) != hipSuccess || sums.alloc((size_t) NV * ngroups) != hipSuccess) {
-        fprintf(stderr, "zeldovich_hip: direct summation: no device memory for %lld partial sums\n", nwg * NV);
-        return 1;
-    }
-    const SweepJumps J = zdsweep::make_sweep_jumps(N);
-    const bool fast = g.genf_tab && !g.phik && !g.qonemode;
-    const long double TWO_PI = 2.0L * 3.14159265358979323846264338327950288L;
-    for (int grp = 0; grp < ngroups; grp++) {
-        DsSites<DS_NS> S;
-        for (int s = 0; s < DS_NS; s++) {  // a short last group sums its first site again; those sums are dropped
-            const int64_t i = (int64_t) grp * DS_NS + s < nsites ? (int64_t) grp * DS_NS + s : (int64_t) grp * DS_NS;
-            S.z[s] = (int) sites_zyx[3 * i], S.y[s] = (int) sites_zyx[3 * i + 1], S.x[s] = (int) sites_zyx[3 * i + 2];
-            const long double a = TWO_PI * (long double) S.z[s] / (long double) N;
-            S.wr[s] = (double) cosl(a), S.wi[s] = (double) sinl(a);
-        }
-        double *partial = part;
-        const size_t per_row = (size_t) ((N + DS_BX - 1) / DS_BX) * NV;
-        int rc = 0;
-        if (fast) {  // the plane ky = 0 (rank 0) through the general form, every other row through the table arithmetic
-            const int skip = rank == 0 ? 1 : 0;
-            if (skip) rc = launch_ds<false>(g, J, S, 0, G, 1, pl->S.lG, pl->ec.vnorm, pl->d_twN, partial, st);
-            if (!rc) rc = launch_ds<true>(g, J, S, rank + skip * G, G, Hq - skip, pl->S.lG, pl->ec.vnorm, pl->d_twN, partial + skip * per_row, st);
-        } else {
-            rc = launch_ds<false>(g, J, S, rank, G, Hq, pl->S.lG, pl->ec.vnorm, pl->d_twN, partial, st);
-        }
-        if (rc || launch_ds_reduce(partial, nwg, sums + (size_t) grp * NV, st)) return 1;
-    }
-    std::vector<double> h((size_t) NV * ngroups);
-    if (hipMemcpyAsync(h.data(), sums, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        fprintf(stderr, "zeldovich_hip: direct summation failed: %s\n", hipGetErrorString(hipGetLastError()));
-        return 1;
-    }
-    std::copy(h.begin(), h.begin() + DS_NQ * nsites, out7);  // [group][site of the group][7] = [site][7]
-    return 0;
+    return zdsweep::ds_sweep_sites(pl, nsites, sites_zyx, pl->ec.vnorm, out7, (hipStream_t) hip_stream);
 }
 
 extern "C" int zd_direct_sum(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, int64_t nsites, const int64_t *sites_zyx,

@@ -20,7 +20,7 @@
 //   Refusals.  Configurations whose Nyquist-plane modes stay alive (the nyquist_dead condition of pack_mode, zd_route.h: there the
 //          delivered fields are not transforms of real fields and "power per wavevector" has no single meaning), and
 //          ZD_Version = 1, whose draws are sequential; ZD_q2LPT jobs, whose delivered fields hold a second-order part the sweep
-//          does not regenerate.
+//          does not regenerate (their band power, order by order: zd_plan_lpt_power, zd_kernels_lpt_ds.hip).
 //
 // A rank sweeps the half-space rows it owns, ky = rank (mod nranks), ky < N/2, every (kx, kz); a row ky >= 1 stands for itself and
 // its Hermitian twin (weight 2), the plane ky = 0 is visited position by position with the conjugate "loser" rule of k_gen.  The

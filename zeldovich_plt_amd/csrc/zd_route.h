@@ -14,7 +14,7 @@
 // Tuning / ablation knobs (environment variables ZD_ABLATE, ZD_PRUNE, ZD_NT, ZD_LAYOUT, ...) exist only in the
 // -DZD_TUNING build (make tuning -> build/libzeldovich_hip_tuning.so, used by scripts/ through ZD_LIB_PATH).
 // The product library never reads the environment: the names do not even reach its binary.  (Global, macro in the product: this
-// header is for zd_capi.cpp alone.)
+// header is for zd_capi.cpp, and for zd_kernels_lpt_ds.hip, which asks the LPT refusals and coefficients.)
 #ifdef ZD_TUNING
 static inline const char *tune_env(const char *name) { return getenv(name); }
 #else

@@ -1,6 +1,6 @@
 // zd_sweep.h — the walk over the modes a plan realises, without transform or store, shared by the band-power sweep
-// (zd_kernels_pk.hip) and the site sums (zd_kernels_ds.hip).  Moved out of k_pk_sweep unchanged; what a sweep does with a mode
-// is the functor it hands to sweep_modes.
+// (zd_kernels_pk.hip), the site sums (zd_kernels_ds.hip) and the sums of the LPT plans (zd_kernels_lpt_ds.hip).  Moved out of
+// k_pk_sweep unchanged; what a sweep does with a mode is the functor it hands to sweep_modes.
 //
 // One thread owns one x and walks the z indices [z0, z1) of the half-space row ky with ONE RNG state (the z-major walk of k_gen at
 // stream factor 1).  FAST = the table arithmetic of k_genf (zd_genmath.h: ln / exp / sincos / sqrt and P(k) from the LDS image T,
@@ -14,6 +14,8 @@
 
 #include "zd_genmath.h"
 
+struct zd_plan;
+
 namespace zdsweep {
 using zd::GenConst;
 using zdpcg::u128;
@@ -26,6 +28,27 @@ struct SweepJumps {
     // z = N/2 wrap of the counter (rows N/2 + 1 .. live at 65536 - N + z, zeldovich.cpp:335); _full: no draw consumed
     zdpcg::Affine next[2], next_full[2];
 };
+
+// Site sums (zd_kernels_ds.hip, zd_kernels_lpt_ds.hip): what the two sweeps over sample sites share
+constexpr int DS_BX = 256;        // threads (consecutive x) per workgroup; a thread walks every z of its row
+constexpr int DS_NS = 8;          // sites per launch
+constexpr int DS_RESEED = 32;     // FAST rows: z steps between two table look-ups of a site's phase
+constexpr int DS_MAX_SITES = 64;
+
+template <int NS>
+struct DsSites {
+    int z[NS], y[NS], x[NS];
+    double wr[NS], wi[NS];  // e^{2 pi i z_s / N}: the rotation of the site's phase per z step
+};
+
+// the sites of launch group grp of a call; a short last group sums its first site again (those sums are dropped)
+DsSites<DS_NS> make_ds_sites(int N, int64_t nsites, const int64_t *sites_zyx, int grp);
+// out[o] = sum of partial[i * nv + o] over the nwg partials of a launch group, o < nv, in an order that depends on nothing but nwg
+int launch_ds_reduce(const double *partial, long long nwg, int nv, double *out, hipStream_t st);
+// k_ds_sweep over this rank's rows of a plan's GenConst for sites already checked, with the ZA velocity factor vnorm, into
+// out7[nsites][7]: what zd_plan_direct_sum does once it has accepted the plan, and the first order of zd_plan_lpt_direct_sum
+// (a ZD_q2LPT plan's first-order velocity factor is lpt2_alpha; its EpiConst::vnorm is 1)
+int ds_sweep_sites(zd_plan *pl, int64_t nsites, const int64_t *sites_zyx, double vnorm, double *out7, hipStream_t st);
 
 inline SweepJumps make_sweep_jumps(int N) {
     SweepJumps J;

@@ -221,6 +221,139 @@ static int self_check(const Writer &w, const zd_param_strings &s, const zd_pk &p
     return 0;
 }
 
+// ZD_LPT_SelfCheck, ZD_LPT_SelfCheck_tol, ZD_LPT_SelfCheck_filename, ZD_LPT_Pk_filename (optional, not in the reference; ZD_q2LPT runs):
+// keys without a member in zd_param_strings, read with zd_param_file_string.  A numeric key is parsed strictly.
+struct LptKeys {
+    int selfcheck = 0;
+    double tol = 0;
+    char selfcheck_filename[1024] = "", pk_filename[1024] = "";
+};
+
+static int refuse(const char *key, const char *value, const char *why) {
+    fprintf(stderr, "Invalid Parameters given: %s = %s %s\n", key, value, why);
+    return 1;
+}
+
+// non-zero (one line on stderr) if the file cannot be read or a key's value is refused
+static int read_lpt_keys(const char *path, LptKeys &k) {
+    char v[1024], old[1024];
+    if (zd_param_file_string(path, "ZD_LPT_SelfCheck", v, sizeof(v))) return 1;
+    if (v[0]) {
+        char *end = nullptr;
+        const long n = strtol(v, &end, 10);
+        if (end == v || *end) return refuse("ZD_LPT_SelfCheck", v, "is not an integer");
+        if (n < 0 || n > 64) return refuse("ZD_LPT_SelfCheck", v, "must lie in 0 ... 64 (sites; 0 = off)");
+        k.selfcheck = (int) n;
+    }
+    if (zd_param_file_string(path, "ZD_LPT_SelfCheck_tol", v, sizeof(v))) return 1;
+    if (v[0]) {
+        char *end = nullptr;
+        k.tol = strtod(v, &end);
+        if (end == v || *end) return refuse("ZD_LPT_SelfCheck_tol", v, "is not a number");
+        if (!(k.tol >= 0)) return refuse("ZD_LPT_SelfCheck_tol", v, "must be >= 0");
+    }
+    if (zd_param_file_string(path, "ZD_LPT_SelfCheck_filename", k.selfcheck_filename, sizeof(k.selfcheck_filename)) ||
+        zd_param_file_string(path, "ZD_LPT_Pk_filename", k.pk_filename, sizeof(k.pk_filename)) ||
+        zd_param_file_string(path, "ZD_SelfCheck", old, sizeof(old)))
+        return 1;
+    if (k.selfcheck > 0 && old[0] && strtol(old, nullptr, 10) != 0)
+        return refuse("ZD_LPT_SelfCheck", v[0] ? v : "n", "does not run together with ZD_SelfCheck: one check keeps the records at the sites");
+    if (zd_param_file_string(path, "ZD_q2LPT", old, sizeof(old))) return 1;
+    if ((k.selfcheck > 0 || k.pk_filename[0]) && strtol(old, nullptr, 10) != 1) {
+        fprintf(stderr, "Invalid Parameters given: %s needs ZD_q2LPT = 1 (it sums the orders of an LPT run)\n",
+                k.selfcheck > 0 ? "ZD_LPT_SelfCheck" : "ZD_LPT_Pk_filename");
+        return 1;
+    }
+    return 0;
+}
+
+// ZD_LPT_Pk_filename: band power of the three orders (zd_lpt_power), one line per non-empty |k| shell
+static int write_lpt_power(const char *path, const zd_params &p, const zd_pk &pk) {
+    const int64_t nb = zd_power_nbins(p.ppd, 1);
+    std::vector<int64_t> count(nb);
+    std::vector<double> sums(8 * (size_t) nb);
+    if (zd_lpt_power(&p, &pk, 1, nb, count.data(), sums.data())) return 1;
+    FILE *f = fopen(path, "w");
+    if (!f) {
+        fprintf(stderr, "Could not open LPT band-power file \"%s\"\n", path);
+        return 1;
+    }
+    fprintf(f, "# k_mean count P_input P_measured disp1_power disp2_power disp3_power disp_power vel_power\n");
+    for (int64_t b = 0; b < nb; b++) {
+        if (count[b] == 0) continue;
+        const double n = (double) count[b];
+        fprintf(f, "%.17g %lld", sums[8 * b] / n, (long long) count[b]);
+        for (int j = 1; j < 8; j++) fprintf(f, " %.17g", sums[8 * b + j] / n);
+        fprintf(f, "\n");
+    }
+    fclose(f);
+    fprintf(stderr, "LPT band power written to %s\n", path);
+    return 0;
+}
+
+// ZD_LPT_SelfCheck = n: the delivered records at the sites of self_check_sites against zd_lpt_direct_sum; returns non-zero if the
+// check fails or cannot be made
+static int lpt_self_check(const Writer &w, const LptKeys &k, const zd_pk &pk) {
+    const zd_params &p = w.p;
+    const int n = (int) w.site_seen.size();
+    std::vector<double> sum(18 * (size_t) n), rec(6 * (size_t) n, NAN);
+    if (zd_lpt_direct_sum(&p, &pk, n, w.sites.data(), sum.data())) return 1;
+    const bool have_vel = p.icformat == ZD_FMT_RVZEL || p.icformat == ZD_FMT_RVDOUBLEZEL;
+    const bool f64 = p.icformat == ZD_FMT_RVDOUBLEZEL || p.icformat == ZD_FMT_ZEL;
+    const double tol = k.tol > 0 ? k.tol : (f64 ? 1e-10 : 1e-6);  // the defaults of ZD_SelfCheck_tol
+    auto total = [&](int i, int col) { return sum[18 * i + col] + sum[18 * i + 6 + col] + sum[18 * i + 12 + col]; };
+    double qmax = 0, m2 = 0, m3 = 0, worst = 0;
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < 3; j++) {
+            qmax = std::max(qmax, fabs(total(i, j)));
+            m2   = std::max(m2, fabs(sum[18 * i + 6 + j]));
+            m3   = std::max(m3, fabs(sum[18 * i + 12 + j]));
+        }
+    for (int i = 0; i < n; i++) {
+        if (!w.site_seen[i]) {
+            fprintf(stderr, "lpt self-check: plane z = %lld was never delivered\n", (long long) w.sites[3 * i]);
+            return 1;
+        }
+        const unsigned char *r = w.site_rec.data() + (size_t) i * w.recsize;
+        const size_t off = p.icformat == ZD_FMT_ZELSIMPLE ? 0 : 8;  // (the record layout: self_check)
+        for (int j = 0; j < (have_vel ? 6 : 3); j++) {
+            double v;
+            if (f64) {
+                memcpy(&v, r + off + 8 * j, 8);
+            } else {
+                float f;
+                memcpy(&f, r + off + 4 * j, 4);
+                v = f;
+            }
+            const int col = j < 3 ? 2 - j : 3 + (5 - j);  // (qz, qy, qx, vz, vy, vx) -> qx, qy, qz, vx, vy, vz
+            rec[6 * i + col] = v;
+            worst = std::max(worst, fabs(v - total(i, col)) / qmax);
+        }
+    }
+    if (k.selfcheck_filename[0]) {
+        FILE *f = fopen(k.selfcheck_filename, "w");
+        if (!f) {
+            fprintf(stderr, "Could not open LPT self-check file \"%s\"\n", k.selfcheck_filename);
+            return 1;
+        }
+        fprintf(f, "# z y x | record: qx qy qz vx vy vz (nan: not delivered) | direct sum, order 1: qx qy qz vx vy vz | order 2 | order 3\n");
+        for (int i = 0; i < n; i++) {
+            fprintf(f, "%lld %lld %lld", (long long) w.sites[3 * i], (long long) w.sites[3 * i + 1], (long long) w.sites[3 * i + 2]);
+            for (int j = 0; j < 6; j++) fprintf(f, " %.17g", rec[6 * i + j]);
+            for (int j = 0; j < 18; j++) fprintf(f, " %.17g", sum[18 * i + j]);
+            fprintf(f, "\n");
+        }
+        fclose(f);
+    }
+    fprintf(stderr, "lpt self-check: %d sites, max |record - direct sum| / max|q| = %.3g, max|psi2| / max|q| = %.3g, max|psi3| / max|q| = %.3g "
+                    "(ZD_LPT_SelfCheck_tol = %g)\n", n, worst, m2 / qmax, m3 / qmax, tol);
+    if (!(worst <= tol)) {
+        fprintf(stderr, "lpt self-check FAILED: the delivered records differ from the direct summation over the three orders\n");
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char *argv[]) {
     if (argc != 2) {
         fprintf(stderr, "Usage: %s param_file\n", argv[0]);
@@ -229,6 +362,8 @@ int main(int argc, char *argv[]) {
     const auto t_start = std::chrono::steady_clock::now();
     auto elapsed = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
 
+    LptKeys lk;  // (asked first: a refusal of these keys is the run's only line)
+    if (read_lpt_keys(argv[1], lk)) exit(1);
     zd_params p;
     zd_param_strings s;
     if (zd_params_from_file(argv[1], &p, &s)) {
@@ -256,11 +391,11 @@ int main(int argc, char *argv[]) {
     static const int recsizes[4] = {32, 32, 56, 12};
     w.recsize     = p.qdensity == 2 ? 0 : recsizes[p.icformat];
     w.plane_bytes = (int64_t) p.ppd * p.ppd * w.recsize;
-    if (s.SelfCheck > 0) {
-        w.sites = self_check_sites(p, s.SelfCheck);
-        w.site_rec.assign((size_t) s.SelfCheck * w.recsize, 0);
-        w.site_dens.assign(s.SelfCheck, 0.f);
-        w.site_seen.assign(s.SelfCheck, 0);
+    if (const int nsites = s.SelfCheck > 0 ? s.SelfCheck : lk.selfcheck) {  // (never both)
+        w.sites = self_check_sites(p, nsites);
+        w.site_rec.assign((size_t) nsites * w.recsize, 0);
+        w.site_dens.assign(nsites, 0.f);
+        w.site_seen.assign(nsites, 0);
     }
     if (p.qdensity) {  // InitOutputBuffers: output.cpp:282-288; "density{:d}" is an fmt pattern on ppd
         std::string name = s.density_filename;
@@ -316,6 +451,8 @@ int main(int argc, char *argv[]) {
     }
     if (s.Pk_measured_filename[0] && write_measured_power(s.Pk_measured_filename, p, pk, eig, eig_ppd)) exit(1);
     if (s.SelfCheck > 0 && self_check(w, s, pk, eig, eig_ppd)) exit(1);
+    if (lk.pk_filename[0] && write_lpt_power(lk.pk_filename, p, pk)) exit(1);
+    if (lk.selfcheck > 0 && lpt_self_check(w, lk, pk)) exit(1);
     w.close_all();
     fprintf(stderr, "WriteParticlesSlab took %.3g sec to write %.3g MB ==> %.3g MB/sec\n", w.seconds,
             w.bytes_written / 1e6, w.bytes_written / 1e6 / (w.seconds > 0 ? w.seconds : 1e-9));
