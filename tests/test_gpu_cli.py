@@ -79,6 +79,33 @@ def test_cli_writes_reference_files(tmp_path, oracle, fmt, R, qd, ngpu):
         assert np.abs(dens - ref["density"]).max() <= 1e-6 * np.abs(ref["density"]).max()
 
 
+def test_cli_refuses_f_nl_at_ppd_8192(tmp_path):
+    """ZD_f_NL at PPD = 8192: the phi round has no 8192-point z lines or f_NL kernels (launch_zfft, launch_fnl_stage end at 4096;
+    tests/test_route_kernels.py).  The command line refuses the job on the host, when the phi round's plan is asked for — before
+    anything is generated — with the refusal that plan has always given; the choosers no longer offer the configuration."""
+    out = tmp_path / "ic"
+    out.mkdir()
+    par = tmp_path / "fnl.par"
+    par.write_text(PAR % dict(cpd=5, fmt="RVZel", out=out, np=8192 ** 3, pk=WMAP, qd=0, R=16) + "ZD_f_NL = 100.0\nZD_n_s = 0.96\nOmega_M = 0.31\n")
+    r = subprocess.run([EXE, str(par)], capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0 and "stream factor 1 invalid for PPD 8192" in r.stderr, r.stderr[-2000:]
+    assert "launch failed" not in r.stderr and not [f for f in out.iterdir() if f.name.startswith("ic_")]
+
+
+def test_cli_refuses_2lpt_dealias_at_ppd_2048(tmp_path):
+    """ZD_2LPT_dealias at PPD = 2048: the round's lattice of 3072 points has no second-order kernels.  The command line shows the
+    route's own refusal, with the stage, the launcher and the key, and generates nothing.  (A store mode cannot be asked for in a
+    parameter file, so the PLT field store below PPD 64 is reached through the API alone: tests/test_gpu_reference_runs.py.)"""
+    out = tmp_path / "ic"
+    out.mkdir()
+    par = tmp_path / "dealias.par"
+    par.write_text(PAR % dict(cpd=5, fmt="RVZel", out=out, np=2048 ** 3, pk=WMAP, qd=0, R=0) + "ZD_q2LPT = 1\nZD_2LPT_dealias = 1\n")
+    r = subprocess.run([EXE, str(par)], capture_output=True, text=True, timeout=60)
+    want = "zeldovich_hip: PPD = 2048: no kernel for the second-order round: x stage of this job (launch_lpt2q_xsrc_t, n = 3072): it is refused at plan creation"
+    assert r.returncode != 0 and want in r.stderr.splitlines(), r.stderr[-2000:]
+    assert "launch failed" not in r.stderr and not [f for f in out.iterdir() if f.name.startswith("ic_")]
+
+
 def test_cli_version1(tmp_path, oracle):
     """`ZD_Version = 1` parameter files (legacy phases; NumBlock scaled by ZD_k_cutoff as src/parameters.cpp:129-141)"""
     n, cpd = 64, 5

@@ -130,10 +130,37 @@ def test_generate_matches_reference_run_on_every_store(zd, tmp_path, name, R, st
     # ZA at stream factor 1: one z-residue per pass, nothing to pair -- every request is served from the reference's arrays (zd::pack_mode)
     ("base", "fields", "reference"), ("base", "packed", "reference"), ("base", "reference", "reference"),
     ("k_cutoff2", "fields", "reference"),
-    # PLT at PPD = 32: the three packed arrays and the reference's four.  Its field store is not requested here: plan creation accepts
-    # it at PPD = 32 although launch_yfft_fields has no 32-point case, and zd_generate does not return from the failed launch -- a
-    # defect of the library (the route should refuse PLT fields below PPD = 64), recorded in DESIGN.md section 6.
+    # PLT at PPD = 32: the three packed arrays and the reference's four.  Its field store does not exist below PPD = 64
+    # (launch_yfft_fields has no 32-point case): the route refuses it at plan creation, test_plt_fields_refused_at_ppd_32 below.
+    # (The error path of a launch that fails in the middle of a step is still open: DESIGN.md section 6.)
     ("plt_rescale", "packed", "packed"), ("plt_rescale", "reference", "reference"),
 ])
 def test_generate_at_ppd_32_and_the_store_it_falls_back_to(zd, tmp_path, name, store_mode, held):
     assert generate_on_store(zd, tmp_path, name, store_mode, 1) == held
+
+
+@pytest.mark.parametrize("name,store_mode", [("plt_rescale", "fields")])
+def test_plt_fields_refused_at_ppd_32(zd, tmp_path, capfd, name, store_mode):
+    """zd.Plan and zd.generate refuse the job at plan creation, on the host, before any launch; stderr names the stage without a kernel"""
+    from oracle import zdo
+    fx = rr.load_fixture(name)
+    eig, _ = rr.write_eigenmodes(str(tmp_path / "eigmodes"), zdo)
+    par = tmp_path / "run.par"
+    par.write_text(rr.fill(fx["par"], tmp_path / "unused", WMAP, tmp_path / "eigmodes"))
+    p, s = zd.params_from_file(str(par))
+    assert int(p.ppd) == 32 and p.qPLT
+    p.store_mode, p.stream_factor = zd.STORE_MODES[store_mode], 1
+    ps = zd.PowerSpectrum.from_file(s.Pk_filename.decode(), p.boxsize, s.Pk_scale, s.Pk_norm, s.Pk_sigma, s.Pk_sigma_ratio, s.Pk_smooth,
+                                    s.qPk_fix_to_mean)
+    before = zd.dispatch_report()
+    want = "no kernel for the y stage of this job (launch_yfft_f_t, N = 32,)"
+    capfd.readouterr()
+    with pytest.raises(RuntimeError, match="zd_plan_create failed"):
+        zd.Plan(p, ps, eig=eig)
+    assert want in capfd.readouterr().err
+    with pytest.raises(RuntimeError, match="zd_generate failed"):
+        zd.generate(p, ps, eig=eig)
+    assert want in capfd.readouterr().err
+    after = zd.dispatch_report()
+    launched = {k: after[k] - before.get(k, 0) for k in after if after[k] != before.get(k, 0) and ("fft" in k[0] or "gen" in k[0])}
+    assert not launched, launched     # refused before the first generator or transform launch

@@ -149,7 +149,8 @@ def test_accepted_jobs_and_memory():
         assert _route_why(zd.make_params(128, q2LPT=1, lpt2_dealias=1, **kw), kw.get("stream_factor", 1))[0] == 0, kw
     # memory: the round peaks at (16 + 8) (3 N / 2)^3 = 81 N^3 bytes (+ the row pad): 87 GB at 1024, 696 GB at 2048
     p = zd.make_params(2048, q2LPT=1, lpt2_dealias=1)
-    assert _route_why(p)[0] == 0                                       # (the route takes it: the lattice 3072 has its transforms)
+    rc, _, why = _route_why(p)                                         # (the lattice 3072 has line transforms, but no k_xlpt2q / k_lpt2q_zsrc)
+    assert rc == 1 and "no kernel for the second-order round: x stage of this job (launch_lpt2q_xsrc_t, n = 3072)" in why, why
     assert L.zd_choose_stream_factor(C.byref(p), 1, BUDGET) == -1
     assert L.zd_choose_stream_factor(C.byref(zd.make_params(2048, q2LPT=1)), 1, BUDGET) > 0
     p = zd.make_params(1024, q2LPT=1, lpt2_dealias=1)

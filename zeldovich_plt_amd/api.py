@@ -93,7 +93,7 @@ EXPORTED_SYMBOLS = [
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
-                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route", "zd_test_lpt2_coefficients", "zd_test_live_handles", "zd_test_plt_matrix"]
+                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route", "zd_test_route_kernels", "zd_test_lpt2_coefficients", "zd_test_live_handles", "zd_test_plt_matrix"]
 STORE_MODES = {"auto": 0, "reference": 1, "packed": 2, "fields": 3}  # zd_params.store_mode (ZD_STORE_*)
 
 _lib = None
@@ -147,6 +147,7 @@ def _load(path, testing):
         L.zd_test_live_handles.argtypes = []
         L.zd_test_live_handles.restype = i64
         L.zd_test_plt_matrix.argtypes = [i64, dbl, i32, i64, vp, vp]
+        L.zd_test_route_kernels.argtypes = [C.POINTER(ZdParams), i32, i32, i32, C.c_char_p, i64]
     L.zd_choose_stream_factor.argtypes = [C.POINTER(ZdParams), C.c_int, i64]
     L.zd_choose_pass_groups.argtypes = [C.POINTER(ZdParams), C.c_int, i64, C.POINTER(i32), C.POINTER(i32)]
     L.zd_plan_create.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, C.c_int, C.c_int, C.POINTER(vp)]
@@ -757,6 +758,27 @@ def test_plt_matrix(n, m_xyz, alpha=2.0, shells=4):
     if L.zd_test_plt_matrix(int(n), float(alpha), int(shells), m.shape[0], m.ctypes.data, out.ctypes.data):
         raise RuntimeError("zd_test_plt_matrix failed")
     return out
+
+
+ROLES = {"main": 0, "phi": 1, "phik": 2, "lpt2_grad": 3}  # zd_route.h ROLE_*
+
+
+def test_route_kernels(params, stream_factor=0, nranks=1, role="main", text=True):
+    """The dispatch tables the stages of a job consult and whether each has a kernel for its key (zd_test_route_kernels; no GPU):
+    {"code": the hook's return value (>= 0: accepted, that many stages without a kernel; -1 refused by the parameters alone; -2 refused
+    only because a stage has no kernel), "accepted", "why", "stages": [(stage, launcher, key, present)]}.  text=False: the code alone."""
+    L = load_testing_library()
+    if not text:
+        return L.zd_test_route_kernels(C.byref(params), stream_factor, nranks, ROLES[role], None, 0)
+    buf = C.create_string_buffer(8192)
+    code = L.zd_test_route_kernels(C.byref(params), stream_factor, nranks, ROLES[role], buf, len(buf))
+    lines = buf.value.decode().splitlines()
+    head = lines[0].split("\t", 2)
+    stages = []
+    for ln in lines[1:]:
+        stage, launcher, key, present = ln.split("\t")
+        stages.append((stage, launcher, key, present == "1"))
+    return {"code": code, "accepted": head[1] == "1", "why": head[2] if len(head) > 2 else "", "stages": stages}
 
 
 def test_v1_words(seed, nblocks):

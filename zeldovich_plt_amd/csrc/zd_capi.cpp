@@ -50,8 +50,9 @@ using zdown::upload;
         }                                                                                            \
     } while (0)
 
-// ---- dispatch diagnostics (zd_launch.h DispatchSite) ----
+// ---- dispatch diagnostics (zd_launch.h DispatchSite) and the depth of the table probes on this thread (zd_launch.h TableProbe) ----
 namespace zd {
+thread_local int table_probe_depth = 0;
 static std::atomic<DispatchSite *> g_dispatch_head{nullptr};
 DispatchSite::DispatchSite(const char *f, int l) : func(f), line(l) {
     DispatchSite *h = g_dispatch_head.load(std::memory_order_relaxed);
@@ -374,6 +375,31 @@ int zd_test_route(const zd_params *p_in, int32_t R, int32_t nranks, int32_t *out
     if (why && cap > 0) snprintf(why, (size_t) cap, "%s", rt.why);
     return rt.ok() ? 0 : 1;
 }
+int zd_test_route_kernels(const zd_params *p_in, int32_t R, int32_t nranks, int32_t role, char *text, int64_t cap) {
+    if (role < zd::ROLE_MAIN || role > zd::ROLE_LPT2_GRAD) return -3;
+    const zd_params pc = zd::canonical(p_in);
+    const Route shape = zd::route_shape(&pc, R, nranks, role), rt = route(&pc, R, nranks, role);
+    zd::StageList st;
+    zd::route_stages(shape, &pc, R, role, nranks, st);
+    int missing = 0;
+    int64_t w = 0;
+    auto put = [&](const char *fmt, ...) {
+        if (!text || w >= cap - 1) return;
+        va_list ap;
+        va_start(ap, fmt);
+        const int n = vsnprintf(text + w, (size_t) (cap - w), fmt, ap);
+        va_end(ap);
+        if (n > 0) w = std::min<int64_t>(cap - 1, w + n);
+    };
+    if (text && cap > 0) text[0] = 0;
+    put("route\t%d\t%s\n", rt.ok() ? 1 : 0, rt.why);
+    for (int i = 0; i < st.n; i++) {
+        missing += st.s[i].present ? 0 : 1;
+        put("%s\t%s\t%s\t%d\n", st.s[i].stage, st.s[i].launcher, st.s[i].key, st.s[i].present ? 1 : 0);
+    }
+    if (rt.ok()) return missing;
+    return shape.ok() ? -2 : -1;
+}
 void zd_test_lpt2_coefficients(const zd_params *p, double *out) {
     out[0] = zd::lpt2_alpha(p);
     out[1] = zd::lpt2_ratio(p);
@@ -411,20 +437,7 @@ static int64_t lpt2_round_bytes(const zd_params *p) {
 static int64_t lpt3_round_bytes(int64_t N) { return N * N * (N + store_row_pad(N)) * 16 + 12 * N * N * N * 8 + lpt2_sk_bytes(N); }
 static int64_t lpt_resident_bytes(const zd_params *p) { return p->q2LPT ? (p->q3LPT ? 5 : 1) * lpt2_sk_bytes(p->ppd) : 0; }
 
-// The two halves of a PLT + density run (zd_route.h plt_dens_split) at the PLT half's stream factor R (<= 0: plan creation's
-// default), and whether their shapes fit together: the PLT half on its field store, the density half density-only with the same
-// passes and the same planes per pass.  (A refusal of either half is not asked here: plan creation then falls back by itself.)
-static bool split_routes(const zd_params *p, int R, zd_params *pa, zd_params *pb, Route *A, Route *B) {
-    *pa = *pb          = *p;
-    pa->qdensity       = 0;
-    *A                 = route(pa, R, 1, zd::ROLE_MAIN);
-    pb->qPLT = pb->qPLTrescale = 0;
-    pb->qdensity       = 2;
-    pb->stream_factor  = 2 * A->R;
-    *B                 = route(pb, 2 * A->R, 1, zd::ROLE_MAIN);
-    return A->family == zd::FAM_COMPOSITE && A->pack == zd::PACK_PLTFIELD && B->family == zd::FAM_COMPOSITE && B->dens_only
-           && B->npass == A->npass && B->pstep == 2 && 2 * B->Zq == A->Zq;
-}
+using zd::split_routes;  // (zd_route.h)
 
 // the smallest stream factor whose stores fit the budget: first among those the family's own kernels take (power-of-two engine,
 // composite kernels on the field stores), then — composite and other even PPDs — on the reference's arrays

@@ -2632,6 +2632,7 @@ static int launch_zfft_t(const JobList &jobs, const StoreLayout &S, int ky0, int
                          const void *twL, void *out, hipStream_t st) {
     constexpr int threads = W * L / E;
     const size_t shmem = sizeof(double) * zdfft::ColsInner<L, W>::SIZE;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_zfft<L, E, W>>(shmem);
     dim3 grid(S.N / W, nky, jobs.n), block(threads);
     hipLaunchKernelGGL((k_zfft<L, E, W>), grid, block, shmem, st, jobs, S, ky0, kyloc0, nky, Zq, (const cplx *) Y,
@@ -2656,7 +2657,7 @@ int launch_zfft(int L, const JobList &jobs, const StoreLayout &S, int ky0, int k
         ZCASE(4096, 16, 4)
     }
 #undef ZCASE
-    fprintf(stderr, "zeldovich_hip: unsupported z-FFT length %d (power of two in [32,4096] required)\n", L);
+    ZD_TABLE_MISS("zeldovich_hip: unsupported z-FFT length %d (power of two in [32,4096] required)\n", L);
     return 2;
 }
 int zfft_tile_width(int L) {
@@ -2675,14 +2676,15 @@ template <int N, int E, int W>
 static int launch_yfft_t(const StoreLayout &S, int nplanes, const void *tw, void *data, hipStream_t st) {
     constexpr int threads = W * N / E;
     const size_t shmem = sizeof(double) * zdfft::ColsInner<N, W>::SIZE;
-    set_dyn_lds<k_yfft<N, E, W, 1, false>>(shmem);
-    set_dyn_lds<k_yfft<N, E, W, 1, true>>(shmem);
     // (lq = 2 with W a multiple of 8 only: the tile is then whole 128-byte lines per row, which the kernel writes back
     // [plane][column] — the order k_xfft_q2_plt reads)
     if (S.lq && (S.lq != 2 || W % 8 != 0 || !S.one_block || nplanes % (1 << S.lq) || (unsigned long long) S.pitch * N * 16ull >= (1ull << 32))) {
-        fprintf(stderr, "zeldovich_hip: plane-interleaved rows need the single-rank store and whole plane groups\n");
+        ZD_TABLE_MISS("zeldovich_hip: plane-interleaved rows need the single-rank store and whole plane groups\n");
         return 2;
     }
+    ZD_PROBE_RETURN();
+    set_dyn_lds<k_yfft<N, E, W, 1, false>>(shmem);
+    set_dyn_lds<k_yfft<N, E, W, 1, true>>(shmem);
     dim3 grid((N << S.lq) / W, S.narray, nplanes >> S.lq), block(threads);
     if (S.one_block) {
         hipLaunchKernelGGL((k_yfft<N, E, W, 1, true>), grid, block, shmem, st, S, (const cplx *) tw, (cplx *) data);
@@ -2698,8 +2700,9 @@ static int launch_zfft_f_t(const FieldLayout &F, const StoreLayout &S, int ky0, 
                            const void *twL, void *out, hipStream_t st) {
     constexpr int W = NC * FIELD_RB, threads = W * L / E;
     const size_t shmem = sizeof(double) * zdfft::ColsInner<L, W>::SIZE;
-    set_dyn_lds<k_zfft_f<L, E, NC>>(shmem);
     if (nky % FIELD_RB || kyloc0 % FIELD_RB) return 2;
+    ZD_PROBE_RETURN();
+    set_dyn_lds<k_zfft_f<L, E, NC>>(shmem);
     dim3 grid(S.N / NC, nky / FIELD_RB, F.nfield), block(threads);
     hipLaunchKernelGGL((k_zfft_f<L, E, NC>), grid, block, shmem, st, F, S, ky0, kyloc0, nky, (const cplx *) Y,
                        (const cplx *) twL, (cplx *) out);
@@ -2735,7 +2738,7 @@ int launch_zfft_fields(int L, const FieldLayout &F, const StoreLayout &S, int ky
         ZCASE(2048, 16, 1)
     }
 #undef ZCASE
-    fprintf(stderr, "zeldovich_hip: field store: unsupported z-FFT length %d (power of two in [32,2048] required)\n", L);
+    ZD_TABLE_MISS("zeldovich_hip: field store: unsupported z-FFT length %d (power of two in [32,2048] required)\n", L);
     return 2;
 }
 
@@ -2748,9 +2751,10 @@ static int launch_yfft_f_t(const FieldLayout &F, const StoreLayout &S, const voi
     // (the attribute is set once per device: for the largest table, one rank's)
     const size_t shmem_max = std::min<size_t>(160 * 1024, sizeof(double) * (zdfft::ColsInner<N, W>::SIZE + (size_t) (N / 2 + FIELD_RB - 1) / FIELD_RB));
     if (shmem > 160 * 1024) {
-        fprintf(stderr, "zeldovich_hip: y stage of the field store needs %zu B of LDS at PPD %d\n", shmem, N);
+        ZD_TABLE_MISS("zeldovich_hip: y stage of the field store needs %zu B of LDS at PPD %d\n", shmem, N);
         return 2;
     }
+    ZD_PROBE_RETURN();
     if constexpr (PERSIST) {
         set_dyn_lds<k_yfft_fp<N, E, W, MINW>>(shmem_max);
         int dev = 0, ncu = 256;
@@ -2798,7 +2802,7 @@ int launch_yfft_fields(const FieldLayout &F, const StoreLayout &S, const void *t
         YCASE(16384, 16, 1)
     }
 #undef YCASE
-    fprintf(stderr, "zeldovich_hip: field store unsupported for PPD %d\n", S.N);
+    ZD_TABLE_MISS("zeldovich_hip: field store unsupported for PPD %d\n", S.N);
     return 2;
 }
 
@@ -2817,7 +2821,7 @@ int launch_yfft(const StoreLayout &S, int nplanes, const void *tw, void *data, h
         YCASE(8192, 16, 2)
     }
 #undef YCASE
-    fprintf(stderr, "zeldovich_hip: unsupported PPD %d (power of two in [32,8192] required)\n", S.N);
+    ZD_TABLE_MISS("zeldovich_hip: unsupported PPD %d (power of two in [32,8192] required)\n", S.N);
     return 2;
 }
 
@@ -2831,13 +2835,14 @@ static int launch_xfft_t(const StoreLayout &S, const EpiConst &ec, const void *t
     const size_t base_dbl = fft_dbl > fld_dbl ? fft_dbl : fld_dbl;
     const size_t shmem = sizeof(double) * (base_dbl > plt_dbl ? base_dbl : plt_dbl);
     if (threads > 1024) {
-        fprintf(stderr, "zeldovich_hip: x pass for PPD %d with %d arrays needs %d threads per workgroup: unsupported\n", N, NA, threads);
+        ZD_TABLE_MISS("zeldovich_hip: x pass for PPD %d with %d arrays needs %d threads per workgroup: unsupported\n", N, NA, threads);
         return 2;
     }
     if (shmem > 160 * 1024) {
-        fprintf(stderr, "zeldovich_hip: x pass for PPD %d with %d arrays needs %zu B of LDS (> 160 KB): unsupported\n", N, NA, shmem);
+        ZD_TABLE_MISS("zeldovich_hip: x pass for PPD %d with %d arrays needs %zu B of LDS (> 160 KB): unsupported\n", N, NA, shmem);
         return 2;
     }
+    ZD_PROBE_RETURN();
     dim3 grid(N / ROWS, nplanes), block(threads);
     if constexpr (NA == 3) {
         if (ec.pack == PACK_PLT3) {
@@ -2858,6 +2863,7 @@ template <int N, int E>
 static int launch_xfft_seq_t(const StoreLayout &S, const EpiConst &ec, const void *tw, const void *data, int plane0,
                              int nplanes, int z_first, int z_step, void *records, Reduce *red, hipStream_t st) {
     const size_t shmem = sizeof(double) * (zdfft::LineInner<N, 1>::SIZE + N);  // + Im of array 2 (k_xfft_seq)
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_xfft_seq<N, E>>(shmem);
     dim3 grid(N, nplanes), block(N / E);
     hipLaunchKernelGGL((k_xfft_seq<N, E>), grid, block, shmem, st, S, ec, (const cplx *) tw, (const cplx *) data, plane0, z_first,
@@ -2870,6 +2876,7 @@ template <int N, int E, bool SPLIT2 = false>
 static int launch_xfft_seq_plt_t(const StoreLayout &S, const EpiConst &ec, const void *tw, const void *data, int plane0,
                                  int nplanes, int z_first, int z_step, void *records, Reduce *red, hipStream_t st) {
     const size_t shmem = sizeof(double) * (zdfft::LineInner<N, 1>::SIZE + (SPLIT2 ? 1 : 2) * N);  // + {vy, vz} (or vz) of array 2
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_xfft_seq_plt<N, E, SPLIT2>>(shmem);
     dim3 grid(N, nplanes), block(N / E);
     hipLaunchKernelGGL((k_xfft_seq_plt<N, E, SPLIT2>), grid, block, shmem, st, S, ec, (const cplx *) tw, (const cplx *) data, plane0, z_first,
@@ -2881,6 +2888,7 @@ static int launch_xfft_seq_plt_t(const StoreLayout &S, const EpiConst &ec, const
 template <int N, int E>
 static int launch_xfft_q2_plt_t(const StoreLayout &S, const EpiConst &ec, const void *tw, const void *data, int plane0, int nplanes,
                                 int z_first, int z_step, void *records, Reduce *red, hipStream_t st) {
+    ZD_PROBE_RETURN();
 #ifdef ZD_TUNING
     if (getenv("ZD_XQ_NP4")) {  // A/B: one workgroup per plane group (all four planes: whole 64-byte pieces per column, one workgroup per CU)
         const size_t sh4 = sizeof(double) * (zdfft::ColsInner<N, 4>::SIZE + 4 * N);
@@ -2910,6 +2918,7 @@ template <int N, int E, bool PLT>
 static int launch_xfft_two_t(const StoreLayout &S, const EpiConst &ec, const void *tw, const void *data, int plane0,
                              int nplanes, int z_first, int z_step, void *records, Reduce *red, hipStream_t st) {
     const size_t shmem = sizeof(double) * zdfft::LineInner<N, 1>::SIZE;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_xfft_two<N, E, PLT>>(shmem);
     for (int emit = 0; emit < 2; emit++) {
         dim3 grid(N, nplanes, (emit != 0) == PLT ? 1 : 2), block(N / E);
@@ -2928,7 +2937,7 @@ int launch_xfft(const StoreLayout &S, const EpiConst &ec, const void *tw, const 
             if (S.N == 1024) return launch_xfft_q2_plt_t<1024, 16>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
             if (S.N == 512) return launch_xfft_q2_plt_t<512, 16>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
         }
-        fprintf(stderr, "zeldovich_hip: no x pass for plane-interleaved rows at PPD %d\n", S.N);
+        ZD_TABLE_MISS("zeldovich_hip: no x pass for plane-interleaved rows at PPD %d\n", S.N);
         return 2;
     }
     // PPD = 8192 with the field store's ring: three lines of a row are 1536 threads / 209 KB of LDS -> one row per
@@ -2983,7 +2992,7 @@ int launch_xfft(const StoreLayout &S, const EpiConst &ec, const void *tw, const 
         XCASE(8192, 16, 1, 1, 1, 1, 1)
     }
 #undef XCASE
-    fprintf(stderr, "zeldovich_hip: unsupported PPD %d\n", S.N);
+    ZD_TABLE_MISS("zeldovich_hip: unsupported PPD %d\n", S.N);
     return 2;
 }
 
@@ -3065,6 +3074,7 @@ int launch_fnl_table(const GenConst &g, int n, void *tab, hipStream_t st) {
 template <int N, int E, int W, int ROWS>
 static int launch_fnl_t(int which, const StoreLayout &S, double f_NL, const void *tw, void *data, void *phik, int nplanes, int lZq,
                         hipStream_t st) {
+    ZD_PROBE_RETURN();
     if (which == 0) {  // x: inverse + nonlinearity + forward
         constexpr int threads = ROWS * N / E;
         const size_t shmem = sizeof(double) * zdfft::LineInner<N, ROWS>::SIZE;
@@ -3107,7 +3117,7 @@ int launch_fnl_stage(int which, const StoreLayout &S, double f_NL, const void *t
         FCASE(4096, 16, 4, 1)
     }
 #undef FCASE
-    fprintf(stderr, "zeldovich_hip: f_NL path supports PPD = 32..4096 (power of two), got %d\n", S.N);
+    ZD_TABLE_MISS("zeldovich_hip: f_NL path supports PPD = 32..4096 (power of two), got %d\n", S.N);
     return 2;
 }
 

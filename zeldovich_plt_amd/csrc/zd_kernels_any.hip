@@ -234,6 +234,7 @@ static int launch_any_cols_t(const AnyTab &tb, void *data, long long batch_strid
                              int zero_point, hipStream_t st) {
     constexpr int E = 16, threads = W * M / E;
     const size_t shmem = sizeof(double) * zdfft::ColsInner<M, W>::SIZE;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_any_cols<M, E, W>>(shmem);
     hipLaunchKernelGGL((k_any_cols<M, E, W>), dim3((ncols + W - 1) / W, nbatch), dim3(threads), shmem, st, tb, (cplx *) data, batch_stride,
                        point_stride, ncols, zero_point);
@@ -244,6 +245,7 @@ template <int M, int W>
 static int launch_any_lines_t(const AnyTab &tb, void *data, long long pitch, long long nlines, hipStream_t st) {
     constexpr int E = 16, threads = W * M / E;
     const size_t shmem = sizeof(double) * zdfft::LineInner<M, W>::SIZE;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_any_lines<M, E, W>>(shmem);
     hipLaunchKernelGGL((k_any_lines<M, E, W>), dim3((unsigned) ((nlines + W - 1) / W)), dim3(threads), shmem, st, tb, (cplx *) data, pitch,
                        nlines);
@@ -260,7 +262,7 @@ int launch_any_cols(const AnyTab &tb, void *data, long long batch_stride, long l
     if (tb.M == m) return launch_any_cols_t<m, wc>(tb, data, batch_stride, point_stride, ncols, nbatch, zero_point, st);
     ANY_SIZES(AC)
 #undef AC
-    fprintf(stderr, "zeldovich_hip: no transform engine of size %d\n", tb.M);
+    ZD_TABLE_MISS("zeldovich_hip: no transform engine of size %d\n", tb.M);
     return 2;
 }
 int launch_any_lines(const AnyTab &tb, void *data, long long pitch, long long nlines, hipStream_t st) {
@@ -268,7 +270,7 @@ int launch_any_lines(const AnyTab &tb, void *data, long long pitch, long long nl
     if (tb.M == m) return launch_any_lines_t<m, wl>(tb, data, pitch, nlines, st);
     ANY_SIZES(AL)
 #undef AL
-    fprintf(stderr, "zeldovich_hip: no transform engine of size %d\n", tb.M);
+    ZD_TABLE_MISS("zeldovich_hip: no transform engine of size %d\n", tb.M);
     return 2;
 }
 int launch_any_scatter(const JobList &jobs, const AnyLayout &A, int ky0, int nky, int L, const void *Y, void *store, hipStream_t st) {

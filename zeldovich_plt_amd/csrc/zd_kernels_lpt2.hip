@@ -313,6 +313,7 @@ template <int N, int E, int ROWS>
 int launch_lpt2_xsrc_t(const StoreLayout &S, int pass, const void *tw, void *data, double *acc, int nplanes, hipStream_t st) {
     constexpr int threads = ROWS * N / E;
     const size_t shmem = sizeof(double) * zdfft::LineInner<N, ROWS>::SIZE;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_xlpt2<N, E, ROWS>>(shmem);
     const double inv = 1. / N / N / N;
     hipLaunchKernelGGL((k_xlpt2<N, E, ROWS>), dim3(N / ROWS, nplanes), dim3(threads), shmem, st, S, pass, inv, (const cplx *) tw, (cplx *) data,
@@ -334,7 +335,7 @@ int launch_gen_lpt2(const GenConst &g, const GenJumps &J, const JobList &jobs, c
     if (g.lpt2 >= 1 && g.lpt2 <= 4 && jobs.n == 2) GCASE(2)
     if (g.lpt2 == 5 && jobs.n == 7 && g.lpt2_sk) GCASE(7)
 #undef GCASE
-    fprintf(stderr, "zeldovich_hip: no second-order generator for pass %d with %d jobs\n", g.lpt2, jobs.n);
+    ZD_TABLE_MISS("zeldovich_hip: no second-order generator for pass %d with %d jobs\n", g.lpt2, jobs.n);
     return 2;
 }
 
@@ -353,7 +354,7 @@ int launch_lpt2_xsrc(const StoreLayout &S, int pass, const void *tw, void *data,
         LCASE(2048, 16, 2)
     }
 #undef LCASE
-    fprintf(stderr, "zeldovich_hip: the second-order round supports PPD = 32..2048 (power of two), got %d\n", S.N);
+    ZD_TABLE_MISS("zeldovich_hip: the second-order round supports PPD = 32..2048 (power of two), got %d\n", S.N);
     return 2;
 }
 

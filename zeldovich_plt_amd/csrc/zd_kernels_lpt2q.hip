@@ -117,6 +117,7 @@ static int launch_lpt2q_xsrc_t(const cplx *tw, int pass, void *data, long long p
     constexpr size_t ld = zdfft::LineQ<P, E, Q, W, true>::LDS_DOUBLES;
     const size_t shmem = sizeof(double) * (ld > (size_t) W * M ? ld : (size_t) W * M);
     if (shmem > 160 * 1024 || pitch < M) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_xlpt2q<P, E, Q, W>>(shmem);
     hipLaunchKernelGGL((k_xlpt2q<P, E, Q, W>), dim3((unsigned) ((nlines + W - 1) / W)), dim3(threads), shmem, st, tw, tw + P, tw + P + M,
                        (cplx *) data, pitch, nlines, pass, 1. / M / M / M, acc);
@@ -128,6 +129,7 @@ static int launch_lpt2q_zsrc_t(const cplx *tw, int N, const void *store, long lo
     constexpr int threads = W * Q * P / E, M = P * Q;
     const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, false>::LDS_DOUBLES;
     if (shmem > 160 * 1024 || 2 * M != 3 * N || N % W || pitch < M) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_lpt2q_zsrc<P, E, Q, W>>(shmem);
     hipLaunchKernelGGL((k_lpt2q_zsrc<P, E, Q, W>), dim3(N / W, N / 2), dim3(threads), shmem, st, tw, tw + P, tw + P + M, (const cplx *) store, pitch,
                        N, (cplx *) sk);
@@ -148,7 +150,7 @@ int launch_lpt2q_xsrc(int m, const void *tw, int pass, void *data, long long pit
     if (m == (p) * (q)) return launch_lpt2q_xsrc_t<p, 16, q, w>((const cplx *) tw, pass, data, pitch, nlines, acc, st);
     LPT2Q_SIZES(XCASE)
 #undef XCASE
-    fprintf(stderr, "zeldovich_hip: the de-aliased second-order round has x lines of 48 .. 1536 points (PPD = 32 .. 1024), got %d\n", m);
+    ZD_TABLE_MISS("zeldovich_hip: the de-aliased second-order round has x lines of 48 .. 1536 points (PPD = 32 .. 1024), got %d\n", m);
     return 2;
 }
 int launch_lpt2q_zsrc(int m, int n, const void *tw, const void *store, long long pitch, void *sk, hipStream_t st) {
@@ -156,7 +158,7 @@ int launch_lpt2q_zsrc(int m, int n, const void *tw, const void *store, long long
     if (m == (p) * (q)) return launch_lpt2q_zsrc_t<p, 16, q, w>((const cplx *) tw, n, store, pitch, sk, st);
     LPT2Q_SIZES(ZCASE)
 #undef ZCASE
-    fprintf(stderr, "zeldovich_hip: the de-aliased second-order round has z lines of 48 .. 1536 points (PPD = 32 .. 1024), got %d\n", m);
+    ZD_TABLE_MISS("zeldovich_hip: the de-aliased second-order round has z lines of 48 .. 1536 points (PPD = 32 .. 1024), got %d\n", m);
     return 2;
 }
 

@@ -376,6 +376,7 @@ template <int N, int E, int ROWS>
 int launch_lpt3_xpair_t(const StoreLayout &S, const void *tw, const void *data, double *td, double *ts, int nplanes, hipStream_t st) {
     constexpr int threads = ROWS * N / E;
     const size_t shmem = sizeof(double) * zdfft::LineInner<N, ROWS>::SIZE;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_xlpt3<N, E, ROWS>>(shmem);
     hipLaunchKernelGGL((k_xlpt3<N, E, ROWS>), dim3(N / ROWS, nplanes), dim3(threads), shmem, st, S, (const cplx *) tw, (const cplx *) data, td, ts);
     ZD_LAUNCH_CHECK();
@@ -386,6 +387,7 @@ template <int N, int E, int ROWS>
 int launch_lpt3_xfwd_t(const StoreLayout &S, const void *tw, const double *src, void *data, int nplanes, hipStream_t st) {
     constexpr int threads = ROWS * N / E;
     const size_t shmem = sizeof(double) * zdfft::LineInner<N, ROWS>::SIZE;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_xfwd3<N, E, ROWS>>(shmem);
     const double inv = 1. / N / N / N;
     hipLaunchKernelGGL((k_xfwd3<N, E, ROWS>), dim3(N / ROWS, nplanes), dim3(threads), shmem, st, S, inv, (const cplx *) tw, src, (cplx *) data);
@@ -406,7 +408,7 @@ int launch_gen_lpt3(const GenConst &g, const GenJumps &J, const JobList &jobs, c
     if (g.lpt3 >= 1 && g.lpt3 <= 6 && jobs.n == 2) GCASE(2)
     if (g.lpt3 == 7 && jobs.n == 7 && g.lpt3_p3 && g.lpt3_c[0] && g.lpt3_c[1] && g.lpt3_c[2]) GCASE(7)
 #undef GCASE
-    fprintf(stderr, "zeldovich_hip: no third-order generator for pass %d with %d jobs\n", g.lpt3, jobs.n);
+    ZD_TABLE_MISS("zeldovich_hip: no third-order generator for pass %d with %d jobs\n", g.lpt3, jobs.n);
     return 2;
 }
 
@@ -424,7 +426,7 @@ int launch_lpt3_xpair(const StoreLayout &S, const void *tw, const void *data, do
         LCASE(1024, 16, 4)
     }
 #undef LCASE
-    fprintf(stderr, "zeldovich_hip: the third-order round supports PPD = 32..1024 (power of two), got %d\n", S.N);
+    ZD_TABLE_MISS("zeldovich_hip: the third-order round supports PPD = 32..1024 (power of two), got %d\n", S.N);
     return 2;
 }
 
@@ -441,7 +443,7 @@ int launch_lpt3_xfwd(const StoreLayout &S, const void *tw, const double *src, vo
         LCASE(1024, 16, 4)
     }
 #undef LCASE
-    fprintf(stderr, "zeldovich_hip: the third-order round supports PPD = 32..1024 (power of two), got %d\n", S.N);
+    ZD_TABLE_MISS("zeldovich_hip: the third-order round supports PPD = 32..1024 (power of two), got %d\n", S.N);
     return 2;
 }
 

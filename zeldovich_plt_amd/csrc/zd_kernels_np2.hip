@@ -492,6 +492,7 @@ static int launch_xdens_q_t(const cplx *tw, const void *dring, int ring_pitch, i
     using LQ = zdfft::LineQ<P, E, Q, 1, true>;
     const size_t shmem = sizeof(double) * (size_t) LQ::LDS_DOUBLES;
     if (shmem > 160 * 1024) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_xdens_q<P, E, Q>>(shmem);
     hipLaunchKernelGGL((k_xdens_q<P, E, Q>), dim3(N, nplanes), dim3(threads), shmem, st, tw, tw + P, tw + P + N, (const cplx *) dring, ring_pitch,
                        density);
@@ -507,6 +508,7 @@ static int launch_zfft_fq_t(const FieldLayout &F, const StoreLayout &S, int ky0,
     static_assert(threads <= 1024, "workgroup too large");
     const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, false>::LDS_DOUBLES;
     if (shmem > 160 * 1024 || nky % FIELD_RB || kyloc0 % FIELD_RB) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_zfft_fq<P, E, Q, NC>>(shmem);
     dim3 grid(S.N / NC, nky / FIELD_RB, F.nfield), block(threads);
     hipLaunchKernelGGL((k_zfft_fq<P, E, Q, NC>), grid, block, shmem, st, F, S, ky0, kyloc0, nky, (const cplx *) Y, tw, tw + P,
@@ -557,7 +559,7 @@ int launch_zfft_fields_np2(int L, const FieldLayout &F, const StoreLayout &S, in
     // workgroups of 128 registers on a CU; with two columns, 432 threads, the z FFT only ran when a generator launch drained: Z stage
     // 10.16 -> 9.42 s, profiles/r05_6912_z_stage.txt)
     if (L == 216) return launch_zfft_fq_t<8, 8, 27, 1>(F, S, ky0, kyloc0, nky, Y, (const cplx *) tw, out, st);
-    fprintf(stderr, "zeldovich_hip: no z transform of length %d (16*2^k * {3, 9, 27, 5, 15, 25, 45, 75, 125, 7, 21, 35, 49}, or one of the short 4 * Q / 8 * Q lengths)\n", L);
+    ZD_TABLE_MISS("zeldovich_hip: no z transform of length %d (16*2^k * {3, 9, 27, 5, 15, 25, 45, 75, 125, 7, 21, 35, 49}, or one of the short 4 * Q / 8 * Q lengths)\n", L);
     return 2;
 }
 // columns per z-FFT workgroup (the generator prunes by it) = the NC of the table above
@@ -578,6 +580,7 @@ static int launch_yfft_fq_t(const FieldLayout &F, const StoreLayout &S, const cp
     static_assert(threads <= 1024, "workgroup too large");
     const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, false>::LDS_DOUBLES;
     if (shmem > 160 * 1024) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_yfft_fq<P, E, Q, W>>(shmem);
     dim3 grid((dens ? 1 : 3) * (N / W), 1, nplanes), block(threads);
     hipLaunchKernelGGL((k_yfft_fq<P, E, Q, W>), grid, block, shmem, st, F, S, tw, tw + P, tw + P + N, (const cplx *) store, plane0,
@@ -604,6 +607,7 @@ static int launch_xfft_q_t(const EpiConst &ec, const cplx *tw, const void *ring,
         constexpr size_t dbl = LQ3::LDS_DOUBLES > stash ? LQ3::LDS_DOUBLES : stash;
         const size_t shmem3 = sizeof(double) * (dbl > (size_t) 18 * threads ? dbl : (size_t) 18 * threads);
         if (shmem3 <= 160 * 1024) {
+            ZD_PROBE_RETURN();
             set_dyn_lds<k_xfft_q3<P, E, Q, PLT>>(shmem3);
             hipLaunchKernelGGL((k_xfft_q3<P, E, Q, PLT>), dim3(N, nplanes), dim3(3 * threads), shmem3, st, ec, tw, tw + P, tw + P + N,
                                (const cplx *) ring, ring_pitch, z_first, z_step, (char *) records, red);
@@ -616,6 +620,7 @@ static int launch_xfft_q_t(const EpiConst &ec, const cplx *tw, const void *ring,
     if constexpr (!PLT) {  // ZA ring: one launch, Im of array 2 parked behind the transform's area
         const size_t need1 = need + sizeof(double) * N, shmem1 = need1 > red_b ? need1 : red_b;
         if (shmem1 <= 160 * 1024) {
+            ZD_PROBE_RETURN();
             set_dyn_lds<k_xfft_seq1_q<P, E, Q>>(shmem1);
             hipLaunchKernelGGL((k_xfft_seq1_q<P, E, Q>), dim3(N, nplanes), dim3(threads), shmem1, st, ec, tw, tw + P, tw + P + N,
                                (const cplx *) ring, ring_pitch, z_first, z_step, (char *) records, red);
@@ -625,6 +630,7 @@ static int launch_xfft_q_t(const EpiConst &ec, const cplx *tw, const void *ring,
     }
     const size_t shmem = need > red_b ? need : red_b;
     if (shmem > 160 * 1024) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_xfft_seq_q<P, E, Q, PLT>>(shmem);
     for (int emit = 0; emit < 2; emit++) {
         dim3 grid(N, nplanes, (emit != 0) == PLT ? 1 : 2), block(threads);
@@ -657,7 +663,7 @@ int launch_yfft_fields_np2(const FieldLayout &F, const StoreLayout &S, const voi
     if (S.N == (p) * (q)) return launch_yfft_fq_t<p, 16, q, w>(F, S, (const cplx *) tw, store, plane0, nplanes, ring_pitch, ring, dens, st);
     NP2_SIZES(YC)
 #undef YC
-    fprintf(stderr, "zeldovich_hip: PPD %d is not among the supported 2^a 3^b sizes\n", S.N);
+    ZD_TABLE_MISS("zeldovich_hip: PPD %d is not among the supported 2^a 3^b sizes\n", S.N);
     return 2;
 }
 int launch_xfft_np2(int N, const EpiConst &ec, const void *tw, const void *ring, int ring_pitch, int nplanes, int z_first, int z_step,
@@ -669,7 +675,7 @@ int launch_xfft_np2(int N, const EpiConst &ec, const void *tw, const void *ring,
                    : launch_xfft_q_t<p, 16, q, false>(ec, (const cplx *) tw, ring, ring_pitch, nplanes, z_first, z_step, records, red, st);
     NP2_SIZES(XC)
 #undef XC
-    fprintf(stderr, "zeldovich_hip: PPD %d is not among the supported 2^a 3^b sizes\n", N);
+    ZD_TABLE_MISS("zeldovich_hip: PPD %d is not among the supported 2^a 3^b sizes\n", N);
     return 2;
 }
 // density planes of `nplanes` store planes from the density ring (k_xdens_q)
@@ -678,7 +684,7 @@ int launch_xdens_np2(int N, const void *tw, const void *dring, int ring_pitch, i
     if (N == (p) * (q)) return launch_xdens_q_t<p, 16, q>((const cplx *) tw, dring, ring_pitch, nplanes, density, st);
     NP2_SIZES(DC)
 #undef DC
-    fprintf(stderr, "zeldovich_hip: no density x pass for PPD = %d on the composite kernels (unsupported size, or its line does not fit the LDS)\n", N);
+    ZD_TABLE_MISS("zeldovich_hip: no density x pass for PPD = %d on the composite kernels (unsupported size, or its line does not fit the LDS)\n", N);
     return 2;
 }
 bool np2_supported_ppd(int N) {
@@ -707,11 +713,13 @@ static int launch_test_fftq_t(int kind, const void *twP, const void *twN, const 
     if (lines % W) return 3;
     if (kind == 1) {
         const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, false>::LDS_DOUBLES;
+        ZD_PROBE_RETURN();
         set_dyn_lds<k_test_fftq_cols<P, E, Q, W>>(shmem);
         hipLaunchKernelGGL((k_test_fftq_cols<P, E, Q, W>), dim3((unsigned) (lines / W)), dim3(threads), shmem, st, (const cplx *) twP,
                            (const cplx *) twN, (const cplx *) twQ, (const cplx *) in, (cplx *) out, lines);
     } else {
         const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, true>::LDS_DOUBLES;
+        ZD_PROBE_RETURN();
         set_dyn_lds<k_test_fftq_lines<P, E, Q, W>>(shmem);
         hipLaunchKernelGGL((k_test_fftq_lines<P, E, Q, W>), dim3((unsigned) (lines / W)), dim3(threads), shmem, st, (const cplx *) twP,
                            (const cplx *) twN, (const cplx *) twQ, (const cplx *) in, (cplx *) out, lines);
@@ -768,7 +776,7 @@ int launch_test_fftq(int n, int kind, const void *twP, const void *twN, const vo
     TC(64, 16, 35, 4) TC(16, 16, 49, 4) TC(128, 16, 49, 2) TC(16, 16, 135, 4) TC(32, 16, 135, 2) TC(64, 16, 135, 1)
     TC(1024, 16, 3, 4)
 #undef TC
-    fprintf(stderr, "zeldovich_hip: no composite FFT for length %d\n", n);
+    ZD_TABLE_MISS("zeldovich_hip: no composite FFT for length %d\n", n);
     return 2;
 }
 #endif  // ZD_TESTING

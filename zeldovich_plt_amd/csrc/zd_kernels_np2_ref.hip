@@ -327,6 +327,7 @@ static int launch_refq_ycols_t(const cplx *tw, const AnyChunks &C, void *data, i
     constexpr int threads = W * Q * P / E;
     const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, false>::LDS_DOUBLES;
     if (shmem > 160 * 1024 || nbatch < 1 || nbatch > 65535) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_refq_ycols<P, E, Q, W>>(shmem);
     hipLaunchKernelGGL((k_refq_ycols<P, E, Q, W>), dim3((ncols + W - 1) / W, nbatch), dim3(threads), shmem, st, tw, tw + P, tw + P + P * Q, C,
                        (cplx *) data, ncols, zero_point, out_limit);
@@ -339,6 +340,7 @@ static int launch_refq_xphi_t(const cplx *tw, void *data, long long pitch, long 
     constexpr size_t ld = zdfft::LineQ<P, E, Q, W, true>::LDS_DOUBLES;
     const size_t shmem = sizeof(double) * (ld > (size_t) W * N ? ld : (size_t) W * N);
     if (shmem > 160 * 1024) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_refq_xphi<P, E, Q, W>>(shmem);
     hipLaunchKernelGGL((k_refq_xphi<P, E, Q, W>), dim3((unsigned) ((nlines + W - 1) / W)), dim3(threads), shmem, st, tw, tw + P, tw + P + N,
                        (cplx *) data, pitch, nlines, f_NL, 1. / N / N / N);
@@ -352,6 +354,7 @@ static int launch_refq_cols_oop_t(const cplx *tw, const void *in, long long in_b
     constexpr int threads = W * Q * P / E;
     const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, false>::LDS_DOUBLES;
     if (shmem > 160 * 1024 || nbatch < 1 || nbatch > 65535) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_refq_cols_oop<P, E, Q, W, CONJ>>(shmem);
     hipLaunchKernelGGL((k_refq_cols_oop<P, E, Q, W, CONJ>), dim3((ncols + W - 1) / W, nbatch), dim3(threads), shmem, st, tw, tw + P,
                        tw + P + P * Q, (const cplx *) in, in_bs, in_ps, (cplx *) out, out_bs, out_ps, ncols);
@@ -363,6 +366,7 @@ static int launch_refq_yphi_t(const cplx *tw, void *store, long long pitch, int 
     constexpr int threads = W * Q * P / E, N = P * Q;
     const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, false>::LDS_DOUBLES;
     if (shmem > 160 * 1024 || nplanes < 1 || nplanes > 65535) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_refq_yphi<P, E, Q, W>>(shmem);
     hipLaunchKernelGGL((k_refq_yphi<P, E, Q, W>), dim3((N + W - 1) / W, nplanes), dim3(threads), shmem, st, tw, tw + P, tw + P + N,
                        (cplx *) store, pitch, f_NL, 1. / N / N / N);
@@ -377,6 +381,7 @@ static int launch_refq_cols_t(const cplx *tw, void *data, long long batch_stride
     static_assert(threads <= 1024, "workgroup too large");
     const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, false>::LDS_DOUBLES;
     if (shmem > 160 * 1024 || nbatch < 1 || nbatch > 65535) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_refq_cols<P, E, Q, W>>(shmem);
     hipLaunchKernelGGL((k_refq_cols<P, E, Q, W>), dim3((ncols + W - 1) / W, nbatch), dim3(threads), shmem, st, tw, tw + P, tw + P + P * Q,
                        (cplx *) data, batch_stride, point_stride, ncols, zero_point);
@@ -389,6 +394,7 @@ static int launch_refq_lines_t(const cplx *tw, void *data, long long pitch, long
     static_assert(threads <= 1024, "workgroup too large");
     const size_t shmem = sizeof(double) * zdfft::LineQ<P, E, Q, W, true>::LDS_DOUBLES;
     if (shmem > 160 * 1024) return 2;
+    ZD_PROBE_RETURN();
     set_dyn_lds<k_refq_lines<P, E, Q, W>>(shmem);
     hipLaunchKernelGGL((k_refq_lines<P, E, Q, W>), dim3((unsigned) ((nlines + W - 1) / W)), dim3(threads), shmem, st, tw, tw + P,
                        tw + P + P * Q, (cplx *) data, pitch, nlines);
@@ -428,7 +434,7 @@ int launch_refq_cols(int n, const void *tw, void *data, long long batch_stride, 
         return launch_refq_cols_t<p, 16, q, w>((const cplx *) tw, data, batch_stride, point_stride, ncols, nbatch, zero_point, st);
     REFQ_SIZES(RC)
 #undef RC
-    fprintf(stderr, "zeldovich_hip: no composite transform of strided lines of length %d\n", n);
+    ZD_TABLE_MISS("zeldovich_hip: no composite transform of strided lines of length %d\n", n);
     return 2;
 }
 int launch_refq_cols_oop(int n, const void *tw, const void *in, long long in_bs, long long in_ps, void *out, long long out_bs, long long out_ps,
@@ -439,7 +445,7 @@ int launch_refq_cols_oop(int n, const void *tw, const void *in, long long in_bs,
                     : launch_refq_cols_oop_t<p, 16, q, w, false>((const cplx *) tw, in, in_bs, in_ps, out, out_bs, out_ps, ncols, nbatch, st);
     REFQ_SIZES(RO)
 #undef RO
-    fprintf(stderr, "zeldovich_hip: no composite transform of strided lines of length %d\n", n);
+    ZD_TABLE_MISS("zeldovich_hip: no composite transform of strided lines of length %d\n", n);
     return 2;
 }
 int launch_refq_yphi(int n, const void *tw, void *store, long long pitch, int nplanes, double f_NL, hipStream_t st) {
@@ -447,7 +453,7 @@ int launch_refq_yphi(int n, const void *tw, void *store, long long pitch, int np
     if (n == (p) * (q)) return launch_refq_yphi_t<p, 16, q, w>((const cplx *) tw, store, pitch, nplanes, f_NL, st);
     REFQ_SIZES(RY)
 #undef RY
-    fprintf(stderr, "zeldovich_hip: no composite phi column transform of length %d\n", n);
+    ZD_TABLE_MISS("zeldovich_hip: no composite phi column transform of length %d\n", n);
     return 2;
 }
 int launch_refq_lines(int n, const void *tw, void *data, long long pitch, long long nlines, hipStream_t st) {
@@ -455,7 +461,7 @@ int launch_refq_lines(int n, const void *tw, void *data, long long pitch, long l
     if (n == (p) * (q)) return launch_refq_lines_t<p, 16, q, w>((const cplx *) tw, data, pitch, nlines, st);
     REFQ_SIZES(RL)
 #undef RL
-    fprintf(stderr, "zeldovich_hip: no composite transform of contiguous lines of length %d\n", n);
+    ZD_TABLE_MISS("zeldovich_hip: no composite transform of contiguous lines of length %d\n", n);
     return 2;
 }
 
@@ -465,7 +471,7 @@ int launch_refq_ycols(int n, const void *tw, const AnyChunks &C, void *data, int
     if (n == (p) * (q) && C.N == n) return launch_refq_ycols_t<p, 16, q, w>((const cplx *) tw, C, data, ncols, nbatch, zero_point, out_limit, st);
     REFQ_SIZES(RYC)
 #undef RYC
-    fprintf(stderr, "zeldovich_hip: no composite transform of chunked y columns of length %d\n", n);
+    ZD_TABLE_MISS("zeldovich_hip: no composite transform of chunked y columns of length %d\n", n);
     return 2;
 }
 int launch_refq_xphi(int n, const void *tw, void *data, long long pitch, long long nlines, double f_NL, hipStream_t st) {
@@ -473,7 +479,7 @@ int launch_refq_xphi(int n, const void *tw, void *data, long long pitch, long lo
     if (n == (p) * (q)) return launch_refq_xphi_t<p, 16, q, w>((const cplx *) tw, data, pitch, nlines, f_NL, st);
     REFQ_SIZES(RXP)
 #undef RXP
-    fprintf(stderr, "zeldovich_hip: no composite phi line transform of length %d\n", n);
+    ZD_TABLE_MISS("zeldovich_hip: no composite phi line transform of length %d\n", n);
     return 2;
 }
 int launch_refq_scatter(const JobList &jobs, const AnyChunks &C, int ky_first, int r0, int nky, int L, const void *Y, void *store, hipStream_t st) {

@@ -30,6 +30,30 @@ struct DispatchSite {
         }                                                                                       \
     } while (0)
 
+// Table probes (zd_tables.h): while a TableProbe is alive on the calling thread, a launcher runs its own dispatch — the case list and
+// the run-time refusals inside the instantiation (threads, LDS, row blocks, plane groups) — and returns 0 where it would launch,
+// before any HIP call; a key without a case returns non-zero without a message.  So "is there a kernel for this key" is answered by
+// the launcher's own code, not by a second list of sizes.  ZD_PROBE_RETURN() stands in every instantiation behind its refusals
+// and in front of set_dyn_lds; ZD_TABLE_MISS is the message of a launcher that found no case.
+namespace zd {
+extern thread_local int table_probe_depth;
+struct TableProbe {
+    TableProbe() { table_probe_depth++; }
+    ~TableProbe() { table_probe_depth--; }
+    TableProbe(const TableProbe &) = delete;
+    TableProbe &operator=(const TableProbe &) = delete;
+};
+inline bool table_probe() { return table_probe_depth > 0; }
+}  // namespace zd
+#define ZD_PROBE_RETURN() \
+    do {                  \
+        if (zd::table_probe()) return 0; \
+    } while (0)
+#define ZD_TABLE_MISS(...)                                    \
+    do {                                                      \
+        if (!zd::table_probe()) fprintf(stderr, __VA_ARGS__); \
+    } while (0)
+
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to (kernel, device): ZD_NumGPU runs one host thread per device through
 // the same launchers, so what has been set is kept per device — a process-wide flag would leave
 // every device but the first with the 64 KB default and the launches of the large-LDS kernels would fail there.

@@ -10,6 +10,7 @@
 #include "../../include/zeldovich_hip.h"
 #include "zd_device.h"
 #include "zd_launch.h"
+#include "zd_tables.h"
 
 // Tuning / ablation knobs (environment variables ZD_ABLATE, ZD_PRUNE, ZD_NT, ZD_LAYOUT, ...) exist only in the
 // -DZD_TUNING build (make tuning -> build/libzeldovich_hip_tuning.so, used by scripts/ through ZD_LIB_PATH).
@@ -215,9 +216,11 @@ inline int min_zlen(int family) { return family == FAM_POW2 ? 32 : family == FAM
 // stream factor 4; every other job keeps 32 (the generators and field-store z transforms of zd_kernels.hip start there)
 inline int given_min_zlen(const zd_params *p, int role) { return p->q2LPT && role == ROLE_MAIN ? 16 : min_zlen(FAM_POW2); }
 
+// route_shape: family, store and shape of a job with the refusals that are arithmetic on the parameters; route() below adds the one
+// that asks the dispatch tables.
 // R <= 0: no factor given — plan creation's default (the first one whose z lines the composite kernels have, else 1).  rank and
 // have_eig take part in plan creation's refusals only.
-inline Route route(const zd_params *p, int R_given, int nranks, int role, int rank = 0, bool have_eig = true) {
+inline Route route_shape(const zd_params *p, int R_given, int nranks, int role, int rank = 0, bool have_eig = true) {
     Route r;
     const int64_t N = p->ppd;
     const int G = nranks < 1 ? 1 : nranks;
@@ -292,6 +295,203 @@ inline Route route(const zd_params *p, int R_given, int nranks, int role, int ra
     r.L         = (int) (N / R);
     r.Hq        = (int) (N / 2) / G;
     r.Zq        = r.L / G;
+    return r;
+}
+
+inline Route route(const zd_params *p, int R_given, int nranks, int role, int rank = 0, bool have_eig = true);
+
+// The two halves of a PLT + density run (plt_dens_split) at the PLT half's stream factor R (<= 0: plan creation's default), and
+// whether their shapes fit together: the PLT half on its field store, the density half density-only with the same passes and the
+// same planes per pass.  (A refusal of either half is not asked here: plan creation then falls back by itself.)
+inline bool split_routes(const zd_params *p, int R, zd_params *pa, zd_params *pb, Route *A, Route *B) {
+    *pa = *pb          = *p;
+    pa->qdensity       = 0;
+    *A                 = route(pa, R, 1, ROLE_MAIN);
+    pb->qPLT = pb->qPLTrescale = 0;
+    pb->qdensity       = 2;
+    pb->stream_factor  = 2 * A->R;
+    *B                 = route(pb, 2 * A->R, 1, ROLE_MAIN);
+    return A->family == FAM_COMPOSITE && A->pack == PACK_PLTFIELD && B->family == FAM_COMPOSITE && B->dens_only
+           && B->npass == A->npass && B->pstep == 2 && 2 * B->Zq == A->Zq;
+}
+
+// ---- which dispatch table every stage of a job consults, and with which key ----
+// One entry per (stage, launcher): the launcher as zd_dispatch_report names its instantiations (a prefix of them: launch_xfft stands
+// for launch_xfft_t, _seq_t, _seq_plt_t, _two_t, _q2_plt_t), the key as it appears among their template arguments, and the answer of
+// the table's predicate (zd_tables.h).  route_stages restates the selection code of the stages — launch_zstage_fft, fused_stage_z,
+// any_stage_z, zd_plan_stage_y_group, zd_plan_stage_x_group, make_phik / zd_plan_phi_xy_group / zd_plan_phi_zfwd, make_lpt2_source,
+// make_lpt3_sources (zd_capi.cpp) — for the plan that plan_create_one builds from a Route; tests/test_gpu_route_edges.py holds it to what
+// a run really launches.  Not listed: the generators (launch_gen takes every z line that is a multiple of 4, which every accepted
+// family's are, and any length on the reference's arrays) and kernels without a size table (scatter, emit, pointwise).
+struct StageKey {
+    char stage[56], launcher[32], key[48];
+    bool present;
+};
+struct StageList {
+    enum { MAX = 48 };
+    int n = 0;
+    StageKey s[MAX];
+    void add(const char *prefix, const char *stage, const char *launcher, bool present, const char *fmt, ...) {
+        if (n >= MAX) return;
+        StageKey &k = s[n++];
+        snprintf(k.stage, sizeof k.stage, "%s%s", prefix, stage);
+        snprintf(k.launcher, sizeof k.launcher, "%s", launcher);
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(k.key, sizeof k.key, fmt, ap);
+        va_end(ap);
+        k.present = present;
+    }
+    const StageKey *first_missing() const {
+        for (int i = 0; i < n; i++)
+            if (!s[i].present) return &s[i];
+        return nullptr;
+    }
+};
+
+// the stages of ONE plan of shape rt (no sub-rounds)
+inline void plan_stages(const Route &rt, const zd_params *p, int role, int nranks, const char *prefix, StageList &out) {
+    const int N = (int) p->ppd, L = rt.L, G = nranks < 1 ? 1 : nranks;
+    const bool phi = role == ROLE_PHI, grad = role == ROLE_LPT2_GRAD;
+    if (rt.family >= FAM_REF_COMPOSITE) {  // the reference's arrays: composite transforms (twr) or convolutions
+        const bool phi_half = phi && rt.twr && G == 1;  // (make_phik: the z lines straight into half-space planes)
+        if (phi_half) out.add(prefix, "z", "launch_refq_cols_oop_t", has_refq_cols_oop(L), "n = %d", L);
+        else if (rt.twr) out.add(prefix, "z", "launch_refq_cols_t", has_refq_cols(L), "n = %d", L);
+        else out.add(prefix, "z", "launch_any_cols_t", has_any_cols(L), "M = %d", any_engine_size(L));
+        if (phi && G > 1) {  // zd_plan_phi_xy_group, zd_plan_phi_zfwd
+            out.add(prefix, "phi y", "launch_refq_ycols_t", has_refq_ycols(N), "n = %d", N);
+            out.add(prefix, "phi x", "launch_refq_xphi_t", has_refq_xphi(N), "n = %d", N);
+            out.add(prefix, "phi z", "launch_refq_cols_oop_t", has_refq_cols_oop(N), "n = %d", N);
+            return;
+        }
+        if (phi_half) {
+            out.add(prefix, "phi x", "launch_refq_lines_t", has_refq_lines(N), "n = %d", N);
+            out.add(prefix, "phi y", "launch_refq_yphi_t", has_refq_yphi(N), "n = %d", N);
+            out.add(prefix, "phi z", "launch_refq_cols_oop_t", has_refq_cols_oop(N), "n = %d", N);
+            return;
+        }
+        if (G > 1) out.add(prefix, "y", "launch_refq_ycols_t", has_refq_ycols(N), "n = %d", N);
+        else if (rt.twr) out.add(prefix, "y", "launch_refq_cols_t", has_refq_cols(N), "n = %d", N);
+        else out.add(prefix, "y", "launch_any_cols_t", has_any_cols(N), "M = %d", any_engine_size(N));
+        if (grad) {  // the de-aliased second-order round on this lattice (make_lpt2_source): N is the lattice, 2 N / 3 the PPD
+            out.add(prefix, "x", "launch_lpt2q_xsrc_t", has_lpt2q_xsrc(N), "n = %d", N);
+            out.add(prefix, "source y", "launch_refq_cols_t", has_refq_cols(N), "n = %d", N);
+            out.add(prefix, "source z", "launch_lpt2q_zsrc_t", has_lpt2q_zsrc(N, 2 * N / 3), "n = %d", N);
+            return;
+        }
+        // x lines: of the main pass, or of the phi round on one rank (x, the 3-D transform back: lines, y columns, z columns)
+        if (rt.twr || G > 1) out.add(prefix, phi ? "phi x" : "x", "launch_refq_lines_t", has_refq_lines(N), "n = %d", N);
+        else out.add(prefix, phi ? "phi x" : "x", "launch_any_lines_t", has_any_lines(N), "M = %d", any_engine_size(N));
+        return;
+    }
+    // slabs of the field stores are whole row blocks (plan_slabs) where the rows of a rank are (the route demotes the store otherwise)
+    const int nky = rt.Hq % FIELD_RB ? rt.Hq : FIELD_RB;
+    if (rt.family == FAM_COMPOSITE) {
+        out.add(prefix, "z", "launch_zfft_fq_t", has_zfft_fields_np2(L, nky), "L = %d", L);
+        if (!rt.dens_only) {
+            out.add(prefix, "y", "launch_yfft_fq_t", has_yfft_fields_np2(N), "N = %d", N);
+            out.add(prefix, "x", "launch_xfft_q_t", has_xfft_np2(N, rt.pack == PACK_PLTFIELD ? PACK_PLT3 : rt.pack), "N = %d, PLT = %s", N,
+                    rt.pack == PACK_PLTFIELD ? "true" : "false");
+        }
+        if (rt.dens) {
+            out.add(prefix, "density y", "launch_yfft_fq_t", has_yfft_fields_np2(N), "N = %d", N);
+            out.add(prefix, "density x", "launch_xdens_q_t", has_xdens_np2(N), "N = %d", N);
+        }
+        return;
+    }
+    // the power-of-two engine
+    const int one_block = G == 1 ? 1 : 0;  // (plan_block_layout: one rank keeps self and twin slots of a plane in one block)
+    if (pack_is_fields(rt.pack)) {
+        out.add(prefix, "z", "launch_zfft_f_t", has_zfft_fields(L, nky), "L = %d,", L);
+        out.add(prefix, "y", "launch_yfft_f_t", has_yfft_fields(N, rt.Hq), "N = %d,", N);
+        // the ring between the y and x stages: three arrays of a single-rank store, PLT3 order for the PLT field store
+        out.add(prefix, "x", "launch_xfft", has_xfft(N, 3, rt.pack == PACK_PLTFIELD ? PACK_PLT3 : rt.pack, 0, 1), "N = %d,", N);
+        return;
+    }
+    out.add(prefix, "z", "launch_zfft_t", has_zfft(L), "L = %d,", L);
+    {   // the fused generator + z FFT of the packed PLT store (plan_block_layout) where the power table allows it (at most 512 spline
+        // segments): plane-interleaved rows, 4 planes; the two-kernel stage on plain rows otherwise — a job needs both
+        const int half = N / 2, kmax = (int) ((double) half * (1.0 / p->k_cutoff) + .5);
+        const bool fused = rt.pack == PACK_PLT3 && p->store_mode == ZD_STORE_AUTO && one_block && genz_plt_supported(N, L) && p->version != 1
+                           && p->qoneslab < 0 && role == ROLE_MAIN && p->k_cutoff >= 1.0 && (kmax == half || !p->corner_modes)
+                           && !tune_env("ZD_NO_FUSED_Z");
+        if (fused) {
+            out.add(prefix, "z fused", "launch_genz_t", genz_plt_supported(N, L), "L = %d, R = %d,", L, rt.R);
+            out.add(prefix, "y fused", "launch_yfft_t", has_yfft(N, 2, one_block, rt.Zq), "N = %d,", N);
+            out.add(prefix, "x fused", "launch_xfft", has_xfft(N, rt.narray, rt.pack, 2, one_block), "N = %d,", N);
+        }
+    }
+    out.add(prefix, "y", "launch_yfft_t", has_yfft(N, 0, one_block, rt.Zq), "N = %d,", N);
+    if (phi) {  // make_phik / zd_plan_phi_xy_group, zd_plan_phi_zfwd: x (inverse, phi + f_NL phi^2, forward), y, z
+        out.add(prefix, "phi x y z", "launch_fnl_t", has_fnl_stage(N), "N = %d,", N);
+        return;
+    }
+    if (grad) {  // make_lpt2_source; make_lpt3_sources runs a plan of the same kind
+        out.add(prefix, "x", "launch_lpt2_xsrc_t", has_lpt2_xsrc(N), "N = %d,", N);
+        out.add(prefix, "source y z", "launch_fnl_t", has_fnl_stage(N), "N = %d,", N);
+        if (p->q3LPT) {
+            out.add(prefix, "third order x", "launch_lpt3_xpair_t", has_lpt3_xpair(N), "N = %d,", N);
+            out.add(prefix, "third order source x", "launch_lpt3_xfwd_t", has_lpt3_xfwd(N), "N = %d,", N);
+        }
+        return;
+    }
+    out.add(prefix, "x", "launch_xfft", has_xfft(N, rt.narray, rt.pack, 0, one_block), "N = %d,", N);
+}
+
+// every stage of the job (p canonical): the plan of shape rt, the rounds that run before its first pass — the f_NL phi round, the
+// second- and third-order rounds — and the density half of a PLT + density run on a composite grid.  A round whose own route is
+// refused is listed with the stage "... route" and the refusal as its key.
+inline void route_stages(const Route &rt, const zd_params *p, int R_given, int role, int nranks, StageList &out) {
+    if (role != ROLE_MAIN) {
+        plan_stages(rt, p, role, nranks, "", out);
+        return;
+    }
+    auto round = [&](const zd_params &pp, int r_role, int r_ranks, const char *prefix) {
+        const Route rr = route(&pp, 1, r_ranks, r_role);
+        const int n0   = out.n;
+        plan_stages(rr, &pp, r_role, r_ranks, prefix, out);
+        bool missing = false;
+        for (int i = n0; i < out.n; i++) missing = missing || !out.s[i].present;
+        if (!rr.legal && !missing) out.add(prefix, "route", "route", false, "%.47s", rr.why);
+    };
+    if (p->f_NL != 0.) {  // make_phik (one rank) / zd_plan_create_phi (several): stream factor 1, no eigenmodes
+        zd_params pp     = *p;
+        pp.stream_factor = 1;
+        pp.qPLT          = 0;
+        round(pp, ROLE_PHI, nranks, "phi round: ");
+    }
+    if (p->q2LPT) {  // make_lpt2_source (with ZD_2LPT_dealias: a plan at the lattice of 3 PPD / 2), make_lpt3_sources
+        zd_params pp     = *p;
+        pp.stream_factor = 1;
+        pp.qoneslab      = -1;
+        if (p->lpt2_dealias) {
+            pp.ppd          = lpt2_dealias_lattice(p->ppd);
+            pp.k_cutoff     = p->k_cutoff * 1.5;
+            pp.nyquist      = p->nyquist * 1.5;
+            pp.lpt2_dealias = 0;
+        }
+        round(pp, ROLE_LPT2_GRAD, 1, "second-order round: ");
+    }
+    zd_params pa, pb;
+    Route A, B;
+    if (plt_dens_split(p, nranks) && split_routes(p, R_given, &pa, &pb, &A, &B) && A.ok() && B.ok()) {
+        plan_stages(A, &pa, role, nranks, "", out);  // (plan_create_ex: the two halves; this route is the fall-back)
+        plan_stages(B, &pb, role, nranks, "density half: ", out);
+        return;
+    }
+    plan_stages(rt, p, role, nranks, "", out);
+}
+
+// The route of a job: its shape, and where nothing else refuses it, whether every stage has a kernel.  A job whose stages lack one is
+// refused here, at plan creation, with the stage and the key named: the launch would otherwise fail with the step half issued.
+inline Route route(const zd_params *p, int R_given, int nranks, int role, int rank, bool have_eig) {
+    Route r = route_shape(p, R_given, nranks, role, rank, have_eig);
+    if (!r.legal) return r;
+    StageList st;
+    route_stages(r, p, R_given, role, nranks, st);
+    if (const StageKey *k = st.first_missing())
+        r.refuse(true, "PPD = %lld: no kernel for the %s stage of this job (%s, %s): it is refused at plan creation", (long long) p->ppd,
+                 k->stage, k->launcher, k->key);
     return r;
 }
 

@@ -13,6 +13,13 @@ extern "C" {
  * pack, narray, pstep, npass, R, L, Hq, Zq, dens, dens_only, composite twiddles; `why` (cap bytes) gets the refusal text, "" if the
  * route is accepted.  Returns 0 if accepted, 1 if refused */
 int zd_test_route(const zd_params *p, int32_t R, int32_t nranks, int32_t *out, char *why, int64_t cap);
+/* the dispatch tables the stages of the job as given consult (zd_route.h route_stages; role: 0 main, 1 phi pass, 2 second f_NL pass,
+ * 3 gradient passes of the second-order round), whatever the route says about the job: `text` (cap bytes) gets the line
+ * "route <TAB> 1 accepted | 0 refused <TAB> refusal", then one line per stage, "stage <TAB> launcher <TAB> key <TAB> 1 | 0" — the launcher
+ * and key as zd_dispatch_report names the instantiation, 1 if the table has a kernel for the key.  text may be NULL.  Returns the
+ * number of stages without a kernel if the route accepts the job; -1 if it is refused by its parameters alone, -2 if only because a
+ * stage has no kernel; -3 for an unknown role */
+int zd_test_route_kernels(const zd_params *p, int32_t R, int32_t nranks, int32_t role, char *text, int64_t cap);
 /* the coefficients a ZD_q2LPT job runs with (zd_route.h): out[0 .. 2] = alpha (= vnorm), lpt2_ratio and lpt2_f2 with their defaults
  * resolved */
 void zd_test_lpt2_coefficients(const zd_params *p, double *out);
