@@ -390,6 +390,48 @@ int zd_lpt_direct_sum(const zd_params *p, const zd_pk *pk, int64_t nsites, const
 int zd_plan_lpt_power(zd_plan *plan, int32_t bin_width, int64_t nbins, int64_t *count, double *sums8, void *hip_stream);
 int zd_lpt_power(const zd_params *p, const zd_pk *pk, int32_t bin_width, int64_t nbins, int64_t *count, double *sums8);
 
+/* ---- glass and other off-lattice particle loads: the delivered field at arbitrary positions ----
+ * Displacements and velocities for particles that do not sit on the PPD^3 lattice (a glass, a tiled glass, BCC / FCC lattices, a
+ * resampled region), by interpolating the delivered records; the definition is pinned in csrc/zd_kernels_glass.hip.  A pure consumer
+ * of delivered planes: every configuration that delivers records is served, and the records are the plan's own (units, vnorm, PLT and
+ * LPT content unchanged).
+ *   positions  pos_xyz: HOST array of npart x (x, y, z) float64 in box units, every coordinate in [0, 1) (x: the fastest index of the
+ *              records, z: the plane index); anything else, NaN included, is refused before the GPU is touched
+ *   order      1: trilinear over the 2^3 surrounding sites; 3: cubic Lagrange over 4^3 sites (it interpolates: at a lattice site the
+ *              result is the record itself)
+ *   results    out6: HOST array of npart x (qx, qy, qz, vx, vy, vz) float64, in the order of the positions; formats without velocities
+ *              (Zeldovich, ZelSimple) leave exact zeros in the velocity columns.  Sums are float64 whatever the record format, every
+ *              particle is owned by one thread (no floating-point atomics): two runs return the same bits.
+ * Accuracy is the caller's choice through oversampling: a run at PPD = m N with ZD_k_cutoff = m holds the band-limited field of the
+ * PPD = N run sampled m times as finely, and the interpolation converges to the exact field as m grows.  No window is divided out.
+ *
+ * The consumer object, for any driver that has device planes: create it for a load, add every plane z in [0, ppd) once, in any order
+ * (d_plane_records: DEVICE pointer to the ppd * ppd records of plane z in the layout of `icformat`, complete by the time work queued
+ * on hip_stream runs; the launches are ordered by that stream), take the result.  About 80 bytes of HBM per particle.  Misuse — a
+ * plane added twice, z outside [0, ppd), a result asked for while planes are missing, NULL arguments — prints one line and returns
+ * non-zero.  The object does not care where a plane comes from, so a one-process-per-GPU driver can use it: each rank keeps an object
+ * for a share of the PARTICLES and shows it every plane, its own and the ones its peers deliver.  zd_displace below drives one GPU. */
+typedef struct zd_interp zd_interp;
+int zd_interp_create(int64_t ppd, int32_t icformat, int32_t order, int64_t npart, const double *pos_xyz, zd_interp **out);
+int zd_interp_add_plane(zd_interp *it, int64_t z, const void *d_plane_records, void *hip_stream);
+int zd_interp_result(zd_interp *it, double *out6);
+void zd_interp_destroy(zd_interp *it);
+/* Every pass of a one-rank plan into the object (store and record buffers of its own, as zd_generate allocates them; each plane's z
+ * from zd_plan_plane_z).  Returns when the planes' work is done.  Refused: plans of several ranks, plans that deliver no records
+ * (ZD_qdensity = 2), an object made for another ppd or ICFormat. */
+int zd_plan_interp(zd_plan *plan, zd_interp *it, void *hip_stream);
+/* The one-call form.  The npart * tile^3 particles of the load replicated tile^3 times — particle ((a tile + b) tile + c) npart + i
+ * sits at (p_i + (c, b, a)) / tile — are processed in sweeps of at most max_particles_per_sweep (0: as many as fit beside the plan in
+ * free HBM); the plan's passes run again for every sweep (the draws are counter-addressed: regeneration is what the library does
+ * anyway), and after each sweep cb receives first_particle, n and the HOST array out6 of n x 6 results, valid during the call (non-zero
+ * return aborts).  A 2048^3-particle tiled glass therefore needs neither a host array nor HBM for all of its particles.  out (may be
+ * NULL): the statistics of the last sweep's run, seconds_total = the whole call.  Refused with one line that names the argument, before
+ * a plan or the GPU is touched: order not 1 or 3, npart < 1, tile < 1, NULL pointers, a position outside [0, 1), ZD_qoneslab >= 0,
+ * ZD_qdensity = 2 (no records are delivered), ngpu > 1.  ZD_qdensity = 1 is accepted; the density plane is ignored. */
+typedef int (*zd_particle_cb)(void *user, int64_t first_particle, int64_t n, const double *out6);
+int zd_displace(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t order, int64_t npart, const double *pos_xyz,
+                int64_t tile, int64_t max_particles_per_sweep, zd_particle_cb cb, void *user, zd_stats *out);
+
 /* ---- diagnostics ------------------------------------------------------------------------------
  * Which kernel variants this process has launched so far, and how often: one line "count<TAB>line<TAB>launcher" per launch
  * site of the library, the launcher named with its template arguments (transform length, elements per thread, tile shape,

@@ -79,6 +79,7 @@ class ZdParamStrings(C.Structure):
 SLAB_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
 GROUP_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
 PASS_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
+PARTICLE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
 
 # every symbol include/zeldovich_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED_SYMBOLS = [
@@ -90,6 +91,7 @@ EXPORTED_SYMBOLS = [
     "zd_dispatch_report", "zd_power_nbins", "zd_plan_measure_power", "zd_measure_power",
     "zd_plan_direct_sum", "zd_direct_sum", "zd_make_eigenmodes", "zd_write_eigmodes", "zd_param_file_string",
     "zd_plan_lpt_direct_sum", "zd_lpt_direct_sum", "zd_plan_lpt_power", "zd_lpt_power",
+    "zd_interp_create", "zd_interp_add_plane", "zd_interp_result", "zd_interp_destroy", "zd_plan_interp", "zd_displace",
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
@@ -204,6 +206,13 @@ def _load(path, testing):
     L.zd_lpt_direct_sum.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), i64, vp, vp]
     L.zd_plan_lpt_power.argtypes = [vp, i32, i64, vp, vp, vp]
     L.zd_lpt_power.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), i32, i64, vp, vp]
+    L.zd_interp_create.argtypes = [i64, i32, i32, i64, vp, C.POINTER(vp)]
+    L.zd_interp_add_plane.argtypes = [vp, i64, vp, vp]
+    L.zd_interp_result.argtypes = [vp, vp]
+    L.zd_interp_destroy.argtypes = [vp]
+    L.zd_interp_destroy.restype = None
+    L.zd_plan_interp.argtypes = [vp, vp, vp]
+    L.zd_displace.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i64, vp, i64, i64, PARTICLE_CB, vp, C.POINTER(ZdStats)]
     L.zd_dispatch_report.argtypes = [C.c_char_p, i64]
     L.zd_dispatch_report.restype = i64
     return L
@@ -546,6 +555,78 @@ def lpt_power(params, ps, bin_width=1):
     return _lpt_power_dict(count, sums)
 
 
+def _position_array(positions):
+    """float64 [npart, 3] of (x, y, z); the range check is the library's (one line on stderr names the particle)"""
+    pos = np.ascontiguousarray(positions, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3 or pos.shape[0] < 1:
+        raise ValueError("positions must be a non-empty [npart, 3] array of (x, y, z) in [0, 1)")
+    return pos
+
+
+def displace(params, ps, positions, order=3, tile=1, eig=None, max_particles_per_sweep=0, stats=None):
+    """Displacements and velocities of a run with these parameters at the positions [npart, 3] of (x, y, z) in box units, each in
+    [0, 1), replicated tile^3 times — a glass, a tiled glass, any off-lattice load (zd_displace on cuda:0; definition in
+    csrc/zd_kernels_glass.hip).  order: 1 = trilinear, 3 = cubic Lagrange.  Returns float64 [npart * tile^3, 6] = qx, qy, qz, vx, vy,
+    vz; particle ((a tile + b) tile + c) npart + i sits at (positions[i] + (c, b, a)) / tile.  stats (a dict): filled with the run's
+    statistics and "sweeps"."""
+    pos = _position_array(positions)
+    total = pos.shape[0] * int(tile) ** 3 if tile >= 1 else 0
+    out = np.zeros((max(total, 0), 6), dtype=np.float64)
+    eigp, eig_ppd = (None, 0)
+    if eig is not None:
+        eig = np.ascontiguousarray(eig, dtype=np.float64)
+        eigp, eig_ppd = eig.ctypes.data, eig.shape[0]
+    sweeps = [0]
+
+    def _cb(user, first, n, outp):
+        sweeps[0] += 1
+        C.memmove(out[first:].ctypes.data, outp, n * 48)
+        return 0
+
+    st = ZdStats()
+    if load_library().zd_displace(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, int(order), pos.shape[0], pos.ctypes.data, int(tile),
+                                  int(max_particles_per_sweep), PARTICLE_CB(_cb), None, C.byref(st)):
+        raise RuntimeError("zd_displace failed; see stderr")
+    if stats is not None:
+        stats.update(_stats_dict(st))
+        stats["sweeps"] = sweeps[0]
+    return out
+
+
+class Interp:
+    """The consumer object of zd_interp_*: create it for a load, add every device plane once, take the result [npart, 6]."""
+
+    def __init__(self, ppd, icformat, positions, order=3):
+        self.L = load_library()
+        self.pos = _position_array(positions)
+        h = C.c_void_p()
+        fmt = ICFORMATS[icformat] if isinstance(icformat, str) else int(icformat)
+        if self.L.zd_interp_create(int(ppd), fmt, int(order), self.pos.shape[0], self.pos.ctypes.data, C.byref(h)):
+            raise RuntimeError("zd_interp_create failed; see stderr")
+        self.h = h
+
+    def add_plane(self, z, d_plane_records, stream=0):
+        if self.L.zd_interp_add_plane(self.h, int(z), d_plane_records, stream):
+            raise RuntimeError("zd_interp_add_plane failed; see stderr")
+
+    def result(self):
+        out = np.zeros((self.pos.shape[0], 6), dtype=np.float64)
+        if self.L.zd_interp_result(self.h, out.ctypes.data):
+            raise RuntimeError("zd_interp_result failed; see stderr")
+        return out
+
+    def close(self):
+        if self.h:
+            self.L.zd_interp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def generate_planes(params, ps, on_plane, eig=None):
     """zd_generate with a per-plane consumer: on_plane(z, records[y, x]) sees a VIEW valid only during the call (like the
     reference's single output buffer); nothing is accumulated here.  Returns the statistics + the number of planes."""
@@ -662,6 +743,16 @@ class Plan:
         if self.L.zd_plan_lpt_power(self.h, int(bin_width), nb, count.ctypes.data, sums.ctypes.data, stream):
             raise RuntimeError("zd_plan_lpt_power failed; see stderr")
         return _lpt_power_dict(count, sums)
+
+    def interp(self, positions, order=3, stream=0):
+        """the plan's field at the positions [npart, 3] (zd_interp_create, zd_plan_interp, zd_interp_result): float64 [npart, 6]"""
+        it = Interp(self.params.ppd, self.params.icformat, positions, order)
+        try:
+            if self.L.zd_plan_interp(self.h, it.h, stream):
+                raise RuntimeError("zd_plan_interp failed; see stderr")
+            return it.result()
+        finally:
+            it.close()
 
     def stats(self):
         st = ZdStats()

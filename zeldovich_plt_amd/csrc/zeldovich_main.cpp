@@ -354,6 +354,117 @@ static int lpt_self_check(const Writer &w, const LptKeys &k, const zd_pk &pk) {
     return 0;
 }
 
+// ZD_Glass_filename, ZD_Glass_tile, ZD_Glass_order, ZD_Glass_output (optional, not in the reference): displacements and velocities for
+// an off-lattice particle load (zd_displace) instead of the lattice's ic_* files; read with zd_param_file_string
+struct GlassKeys {
+    char filename[1024] = "", output[1024] = "";
+    long tile = 1, order = 3;
+    std::vector<double> pos;  // the load: (x, y, z) per particle
+};
+
+// non-zero (one line on stderr) if the file cannot be read, a key's value is refused or the load cannot be used
+static int read_glass_keys(const char *path, GlassKeys &k) {
+    char tile[1024], order[1024];
+    if (zd_param_file_string(path, "ZD_Glass_filename", k.filename, sizeof(k.filename)) || zd_param_file_string(path, "ZD_Glass_tile", tile, sizeof(tile)) ||
+        zd_param_file_string(path, "ZD_Glass_order", order, sizeof(order)) || zd_param_file_string(path, "ZD_Glass_output", k.output, sizeof(k.output)))
+        return 1;
+    if (!k.filename[0]) {
+        const char *other = tile[0] ? "ZD_Glass_tile" : order[0] ? "ZD_Glass_order" : k.output[0] ? "ZD_Glass_output" : nullptr;
+        if (other) {
+            fprintf(stderr, "Invalid Parameters given: %s needs ZD_Glass_filename (the particle load it applies to)\n", other);
+            return 1;
+        }
+        return 0;
+    }
+    char *end = nullptr;
+    if (tile[0]) {
+        k.tile = strtol(tile, &end, 10);
+        if (end == tile || *end) return refuse("ZD_Glass_tile", tile, "is not an integer");
+        if (k.tile < 1 || k.tile > 65536) return refuse("ZD_Glass_tile", tile, "must lie in 1 ... 65536");
+    }
+    if (order[0]) {
+        k.order = strtol(order, &end, 10);
+        if (end == order || *end) return refuse("ZD_Glass_order", order, "is not an integer");
+        if (k.order != 1 && k.order != 3) return refuse("ZD_Glass_order", order, "must be 1 (trilinear) or 3 (cubic Lagrange)");
+    }
+    std::error_code ec;
+    const uintmax_t size = fs::file_size(k.filename, ec);
+    if (ec) {
+        fprintf(stderr, "Invalid Parameters given: ZD_Glass_filename = %s cannot be read\n", k.filename);
+        return 1;
+    }
+    if (size == 0 || size % 24) {
+        fprintf(stderr, "Invalid Parameters given: ZD_Glass_filename = %s holds %llu bytes: float64 triples (x, y, z) make a multiple of 24\n", k.filename,
+                (unsigned long long) size);
+        return 1;
+    }
+    k.pos.resize(size / 8);
+    FILE *f = fopen(k.filename, "rb");
+    const size_t got = f ? fread(k.pos.data(), 8, k.pos.size(), f) : 0;
+    if (f) fclose(f);
+    if (got != k.pos.size()) {
+        fprintf(stderr, "Invalid Parameters given: ZD_Glass_filename = %s cannot be read\n", k.filename);
+        return 1;
+    }
+    for (size_t i = 0; i < k.pos.size(); i++)
+        if (!(k.pos[i] >= 0.0 && k.pos[i] < 1.0)) {
+            fprintf(stderr, "Invalid Parameters given: ZD_Glass_filename = %s: particle %llu = (%.17g, %.17g, %.17g) lies outside [0, 1)^3\n", k.filename,
+                    (unsigned long long) (i / 3), k.pos[i / 3 * 3], k.pos[i / 3 * 3 + 1], k.pos[i / 3 * 3 + 2]);
+            return 1;
+        }
+    return 0;
+}
+
+// one sweep of zd_displace into the output file: float64[9] per particle = position, displacement, velocity, in index order
+struct GlassWriter {
+    const GlassKeys *k = nullptr;
+    FILE *f = nullptr;
+    int64_t npart = 0, sweeps = 0;
+    static int callback(void *user, int64_t first, int64_t n, const double *out6) {
+        GlassWriter *w = (GlassWriter *) user;
+        const int64_t t = w->k->tile;
+        std::vector<double> row(9 * (size_t) std::min<int64_t>(n, 1 << 16));
+        for (int64_t i0 = 0; i0 < n; i0 += 1 << 16) {
+            const int64_t m = std::min<int64_t>(n - i0, 1 << 16);
+            for (int64_t i = 0; i < m; i++) {
+                const int64_t g = first + i0 + i, cell = g / w->npart, b = g % w->npart;
+                const double off[3] = {(double) (cell % t), (double) ((cell / t) % t), (double) (cell / (t * t))};
+                for (int j = 0; j < 3; j++) row[9 * i + j] = (w->k->pos[3 * b + j] + off[j]) / (double) t;
+                memcpy(&row[9 * i + 3], out6 + 6 * (i0 + i), 6 * sizeof(double));
+            }
+            if (fwrite(row.data(), 72, (size_t) m, w->f) != (size_t) m) {
+                fprintf(stderr, "Short write on the glass output file\n");
+                return 1;
+            }
+        }
+        w->sweeps++;
+        return 0;
+    }
+};
+
+// the run of a parameter file with ZD_Glass_filename: the planes feed the interpolation, no lattice file is written
+static int glass_run(const GlassKeys &gk, const zd_params &p, const zd_param_strings &s, const zd_pk &pk, const double *eig, int64_t eig_ppd) {
+    const fs::path out = gk.output[0] ? fs::path(gk.output) : fs::path(s.output_dir) / "ic_glass";
+    GlassWriter w;
+    w.k     = &gk;
+    w.npart = (int64_t) gk.pos.size() / 3;
+    w.f     = fopen(out.c_str(), "wb");
+    if (!w.f) {
+        fprintf(stderr, "Could not open output file \"%s\"\n", out.c_str());
+        return 1;
+    }
+    zd_stats st;
+    memset(&st, 0, sizeof(st));
+    const int rc = zd_displace(&p, &pk, eig, eig_ppd, (int32_t) gk.order, w.npart, gk.pos.data(), gk.tile, 0, GlassWriter::callback, &w, &st);
+    if (fclose(w.f) || rc) {
+        fprintf(stderr, "zeldovich: the glass run failed\n");
+        return 1;
+    }
+    fprintf(stderr, "glass: %lld particles, order %ld, %lld sweeps\n", (long long) (w.npart * gk.tile * gk.tile * gk.tile), gk.order, (long long) w.sweeps);
+    fprintf(stderr, "Displacements at the particles took %f seconds (stream factor %d); written to %s\n", st.seconds_total, st.stream_factor, out.c_str());
+    return 0;
+}
+
 int main(int argc, char *argv[]) {
     if (argc != 2) {
         fprintf(stderr, "Usage: %s param_file\n", argv[0]);
@@ -364,6 +475,8 @@ int main(int argc, char *argv[]) {
 
     LptKeys lk;  // (asked first: a refusal of these keys is the run's only line)
     if (read_lpt_keys(argv[1], lk)) exit(1);
+    GlassKeys gk;
+    if (read_glass_keys(argv[1], gk)) exit(1);
     zd_params p;
     zd_param_strings s;
     if (zd_params_from_file(argv[1], &p, &s)) {
@@ -397,7 +510,11 @@ int main(int argc, char *argv[]) {
         w.site_dens.assign(nsites, 0.f);
         w.site_seen.assign(nsites, 0);
     }
-    if (p.qdensity) {  // InitOutputBuffers: output.cpp:282-288; "density{:d}" is an fmt pattern on ppd
+    if (gk.filename[0] && (s.SelfCheck > 0 || lk.selfcheck > 0)) {
+        fprintf(stderr, "Invalid Parameters given: ZD_Glass_filename does not run together with ZD_SelfCheck / ZD_LPT_SelfCheck: no lattice records are kept\n");
+        exit(1);
+    }
+    if (p.qdensity && !gk.filename[0]) {  // InitOutputBuffers: output.cpp:282-288; "density{:d}" is an fmt pattern on ppd
         std::string name = s.density_filename;
         const size_t pos = name.find("{:d}");
         if (pos != std::string::npos) name.replace(pos, 4, std::to_string((long long) p.ppd));
@@ -427,6 +544,14 @@ int main(int argc, char *argv[]) {
     if (p.k_cutoff != 1)
         fprintf(stderr, "Using k_cutoff = %f (effective ppd = %d)\n", p.k_cutoff, (int) (p.ppd / p.k_cutoff + .5));
     fprintf(stderr, "Preamble took %f seconds\n", elapsed());
+
+    if (gk.filename[0]) {  // an off-lattice load: the run's planes feed the interpolation
+        if (glass_run(gk, p, s, pk, eig, eig_ppd)) exit(1);
+        if (eig) zd_free(eig);
+        zd_pk_destroy(pkh);
+        fprintf(stderr, "zeldovich took %.4g sec for ppd %lld\n", elapsed(), (long long) p.ppd);
+        return 0;
+    }
 
     zd_stats st;
     memset(&st, 0, sizeof(st));
