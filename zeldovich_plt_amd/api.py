@@ -95,7 +95,8 @@ EXPORTED_SYMBOLS = [
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
-                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route", "zd_test_route_kernels", "zd_test_lpt2_coefficients", "zd_test_live_handles", "zd_test_plt_matrix"]
+                   "zd_test_fft", "zd_test_ycols", "zd_test_poison", "zd_test_route", "zd_test_route_kernels", "zd_test_lpt2_coefficients", "zd_test_live_handles", "zd_test_plt_matrix",
+                   "zd_test_ring_pair_w"]
 STORE_MODES = {"auto": 0, "reference": 1, "packed": 2, "fields": 3}  # zd_params.store_mode (ZD_STORE_*)
 
 _lib = None
@@ -144,6 +145,8 @@ def _load(path, testing):
         L.zd_test_ycols.argtypes = [i32, i32, i32, i32, i32, vp, vp]
         L.zd_test_poison.argtypes = [C.c_int]
         L.zd_test_poison.restype = None
+        L.zd_test_ring_pair_w.argtypes = [C.c_int]
+        L.zd_test_ring_pair_w.restype = None
         L.zd_test_lpt2_coefficients.argtypes = [C.POINTER(ZdParams), vp]
         L.zd_test_lpt2_coefficients.restype = None
         L.zd_test_live_handles.argtypes = []

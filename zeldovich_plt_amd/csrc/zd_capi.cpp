@@ -90,6 +90,10 @@ int64_t zd_dispatch_report(char *buf, int64_t cap) {
 #ifdef ZD_TESTING
 static std::atomic<int> g_poison{0};
 void zd_test_poison(int on) { g_poison.store(on); }
+// w = 4: plans of the ZA field store at PPD = 1024 created from now on pair their ring rows in groups of 4 (two pairs per y workgroup,
+// the form PPD = 4096 runs) instead of ring_pair_w's 8; 0: back to the table
+static std::atomic<int> g_ring_pair_w{0};
+void zd_test_ring_pair_w(int w) { g_ring_pair_w.store(w); }
 #endif
 hipError_t zd_store_alloc(void **p, size_t bytes) {
     hipError_t e = hipMalloc(p, bytes);
@@ -1165,6 +1169,7 @@ static int plan_block_layout(zd_plan *pl, bool v1) {
                       && g.genf_tab && !v1 && p->qoneslab < 0 && main && p->k_cutoff >= 1.0
                       && (g.kmax == pl->half || !p->corner_modes) && (S.prune & 7) == 7 && !tune_env("ZD_NO_FUSED_Z");
         S.lq         = pl->fused_z ? 2 : 0;
+        S.paired     = 0;  // (set with the field store's ring, plan_store)
         // (the pad that spreads the y stage's strided rows over the HBM channels: 24 elements per plain row; per plane row of an
         // interleaved row 12 measured best — y stage of PPD=2048 PLT 144.5 ms at 24, 143.2 at 6, 139.7 at 12, 156.7 at 48)
         if (S.lq && !tune_env("ZD_PAD")) row_pad = store_row_pad(pl->N) / 2;
@@ -1274,6 +1279,12 @@ static int plan_stores(zd_plan *pl, bool twr) {
     pl->store_bytes_  = pl->F.chunk_elems * pl->nranks * 16;
     // ring: `ring_planes` store planes of the three arrays, laid out as a single-rank block store (one_block)
     pl->ring_planes = field_ring_planes(pl->N, pl->Zq);
+    // the ZA potentials at the sizes whose ring k_xfft_seq consumes: the y stage computes the columns x and N - x from one fetch and
+    // writes them side by side (zd_device.h ring_pair_w).  The y launch takes the store's layout, the x launch the ring's: both say so
+    S.paired = pl->pack == zd::PACK_ZAFIELD && pl->F.nfield == 4 ? zd::ring_pair_w(pl->N) : 0;
+#ifdef ZD_TESTING
+    if (S.paired && pl->N == 1024 && g_ring_pair_w.load() == 4) S.paired = 4;  // zd_test_ring_pair_w
+#endif
     zd::StoreLayout &Q = pl->SR;
     Q            = S;
     Q.lq         = 0;
@@ -2566,6 +2577,7 @@ int zd_test_yfft_variant(int32_t n, int32_t variant, int32_t narray, int32_t npl
         while ((1 << lBz) > nplanes) lBz--;
     }
     S.lq = 0;
+    S.paired = 0;
     S.lBk = lBk; S.lBz = lBz; S.rows_outer = 0; S.one_block = 0; S.pitch = n; S.prune = 0; S.nt = 0; S.kmax = 0; S.fund2 = 0; S.k2_cutoff = 0;
     S.a_rows = (1 << lBk) << lBz;
     S.zb_rows = S.a_rows * narray;

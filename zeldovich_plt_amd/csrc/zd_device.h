@@ -153,7 +153,30 @@ struct StoreLayout {
     // 64-byte runs (4 planes x 16 B) instead of 16-byte pieces, the y stage's 8-line tile is 2 columns x 4 planes = one 128-byte
     // line, the x stage transforms the lines of a plane pair side by side.  0 everywhere else.
     int lq;
+    // Paired ring rows (ring_pair_w below): W when the y stage of the ZA field store writes the columns x and N - x of this ring
+    // side by side, 0 for plain rows (every store but that ring).
+    int paired;
 };
+
+// Paired ring rows.  The y stage of the ZA field store computes column x < N/2 and its mirror N - x from ONE fetch of the potentials
+// (zd_kernels.hip k_yfft_f, PAIR): a workgroup of W lines holds the W/2 columns x0 .. x0 + W/2 - 1 and their mirrors, and writes them as
+// one run of W ring elements.  A ring row is therefore cut into groups of W elements: group j holds x = j W/2 + i (i < W/2) at position
+// j W + i and N - x at position j W + W - 1 - i (consecutive x > N/2 are consecutive addresses of a half group).  Position W - 1 of group
+// 0, the mirror slot of x = 0, stands for column N/2, which the zero rule always kills: the y stage writes zeros there.
+// W per N — the W of launch_yfft_fields' table at the sizes whose ring k_xfft_seq consumes and whose W is at least 4; 0: plain rows.
+constexpr int ring_pair_w(int N) { return N == 4096 ? 4 : (N == 2048 || N == 1024 ? 8 : 0); }
+// position of column x in a paired row of N elements, W a power of two >= 2
+ZD_HD int ring_pair_pos(int N, int W, int x) {
+    const int h = W >> 1, m = x < N / 2 ? x : (N - x) & (N / 2 - 1);  // (x = N/2 -> 0: the mirror slot of column 0)
+    const int g2 = 2 * (m & ~(h - 1)), i = m & (h - 1);                // first position of the group, index inside the half group
+    return x < N / 2 ? g2 + i : g2 + W - 1 - i;
+}
+// ... and the column that position p holds (the mirror slot of column 0: N/2)
+ZD_HD int ring_pair_col(int N, int W, int p) {
+    const int h = W >> 1, i = p & (W - 1), g = (p & ~(W - 1)) >> 1;  // first column of the group
+    const int m = g + (i < h ? i : W - 1 - i);
+    return i < h ? m : (m ? N - m : N / 2);
+}
 
 // StoreLayout::prune bit: the y stage skips whole column tiles without a live row.  Set only together with
 // EpiConst::xdead_lo / hi, i.e. when the consumer of the y stage's output takes zeros for those columns (k_xfft*); the f_NL phi
@@ -348,10 +371,27 @@ struct Reduce {
 // by their linear index and every XCD has its own L2, so the workgroups that read or write the same lines are made neighbours ON
 // ONE XCD: the TPL tiles of a 128-byte ring line (W < 8), their mirror images (rows y > N/2 are read at column N - x: a tile's
 // mirrored reads are its mirror tile's direct reads, off by one column), for each of the three arrays.
-template <int NT, int W>
+// PAIR (paired ring rows, ring_pair_w): a tile is W/2 columns of the half x < N/2 WITH their mirrors, so there are no mirror tiles to
+// place: per XCD, the TPL tiles of a 128-byte ring line x the three arrays, group after group.
+template <int NT, int W, bool PAIR = false>
 __device__ __forceinline__ void ytile_of(int id, int &tile, int &a) {
     constexpr int TPL = W >= 8 ? 1 : 8 / W, GS = 6 * TPL;
-    if constexpr (NT % (16 * TPL) == 0) {
+    if constexpr (PAIR) {
+        static_assert(NT % (8 * TPL) == 0, "paired y tiles: whole groups per XCD");
+#ifndef ZD_YPAIR_ORDER
+#define ZD_YPAIR_ORDER 0
+#endif
+        if constexpr (ZD_YPAIR_ORDER == 1) {  // A/B (make variant FLAGS=-DZD_YPAIR_ORDER=1): array by array over the whole plane
+            const int r = id % NT, xcd = r & 7, s = r >> 3;
+            a    = id / NT;
+            tile = TPL * ((s / TPL) * 8 + xcd) + s % TPL;
+        } else {
+            const int xcd = id & 7, s = id >> 3;
+            const int g = (s / (3 * TPL)) * 8 + xcd, m = s % (3 * TPL);
+            a    = m / TPL;
+            tile = TPL * g + m % TPL;
+        }
+    } else if constexpr (NT % (16 * TPL) == 0) {
         const int xcd = id & 7, s = id >> 3;  // s: position in this XCD's stream
         // (groups interleaved over the XCDs; giving each XCD a contiguous range of groups measured 12 % slower)
         const int g = (s / GS) * 8 + xcd, m = s % GS;  // group of 2*TPL tiles, member

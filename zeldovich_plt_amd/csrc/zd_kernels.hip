@@ -1426,12 +1426,12 @@ __global__ __launch_bounds__(NC *FIELD_RB *L / E) void k_zfft_f(FieldLayout F, S
 // TWO: the array is made of two potentials (a = 2, and every PLT array).  Compiled as two separate bodies so that the
 // one-potential arrays (two thirds of the ZA workgroups) keep their E loads in flight without the register pressure of the
 // second potential's batches.
-template <int N, int E, int W, bool TWO>
+template <int N, int E, int W, bool TWO, bool PAIR>
 __device__ __forceinline__ void yfft_f_unit_t(const FieldLayout &F, const StoreLayout &S, const cplx *__restrict__ tw,
                                               const cplx *__restrict__ store, int plane0, int ring_pitch, cplx *__restrict__ ring,
                                               int tile, int a, int pz, int unit, int t, int w, double *lds);
 
-template <int N, int E, int W>
+template <int N, int E, int W, bool PAIR>
 __device__ __forceinline__ void yfft_f_unit(const FieldLayout &F, const StoreLayout &S, const cplx *__restrict__ tw,
                                             const cplx *__restrict__ store, int plane0, int ring_pitch, cplx *__restrict__ ring,
                                             int id, int pz, int t, int w, double *lds) {
@@ -1440,22 +1440,31 @@ __device__ __forceinline__ void yfft_f_unit(const FieldLayout &F, const StoreLay
     constexpr int T = PL::T;
     constexpr int NT = N / W;
     int tile, a;
-    ytile_of<NT, W>(id, tile, a);
+    ytile_of<NT, W, PAIR>(id, tile, a);
     const int unit = pz * 3 * NT + id;
     if (F.nfield == 6 || a == 2)  // workgroup-uniform
-        yfft_f_unit_t<N, E, W, true>(F, S, tw, store, plane0, ring_pitch, ring, tile, a, pz, unit, t, w, lds);
+        yfft_f_unit_t<N, E, W, true, PAIR>(F, S, tw, store, plane0, ring_pitch, ring, tile, a, pz, unit, t, w, lds);
     else
-        yfft_f_unit_t<N, E, W, false>(F, S, tw, store, plane0, ring_pitch, ring, tile, a, pz, unit, t, w, lds);
+        yfft_f_unit_t<N, E, W, false, PAIR>(F, S, tw, store, plane0, ring_pitch, ring, tile, a, pz, unit, t, w, lds);
 }
 
-template <int N, int E, int W, bool TWO>
+template <int N, int E, int W, bool TWO, bool PAIR>
 __device__ __forceinline__ void yfft_f_unit_t(const FieldLayout &F, const StoreLayout &S, const cplx *__restrict__ tw,
                                               const cplx *__restrict__ store, int plane0, int ring_pitch, cplx *__restrict__ ring,
                                               int tile, int a, int pz, [[maybe_unused]] int unit, int t, int w, double *lds) {
     using PL  = zdfft::Plan<N, E>;
     using LDS = zdfft::ColsInner<N, W>;
     constexpr int T = PL::T;
-    const int x = tile * W + w, xm = (N - x) & (N - 1);
+    // PAIR (paired ring rows, zd_device.h ring_pair_w; ZA only): the tile is the W/2 columns x0 .. x0 + W/2 - 1 of the half kx < N/2.
+    // Line w < W/2 is column x0 + w as ever ("S"); line w >= W/2 is the "D" line of column x0 + (W - 1 - w): the SAME completed line U
+    // (lanes w and W - 1 - w load the same addresses) with ky entering with the opposite sign, and conjugated when it is stored —
+    //   A(N - x) = conj FFT_y[(i kx + ky) U],   C(N - x) = conj FFT_y[i U0 + U1]
+    // (conj f(-ky) transforms to conj FFT(f), and the completed line of column N - x is conj U(-ky), -conj U(-ky) for the Z pair) —
+    // which is column N - x of today's array: ring element tile * W + w holds it.  Every potential is read by one workgroup.
+    static_assert(!PAIR || (W >= 2 && N / 2 % (W / 2) == 0), "paired tiles: whole half groups");
+    const bool dline = PAIR && w >= W / 2;
+    const int x = PAIR ? tile * (W / 2) + (dline ? W - 1 - w : w) : tile * W + w, xm = (N - x) & (N - 1);
+    // (the D line's signs are selects on `dline`, a lane mask in scalar registers: the kernel has no vector register to spare)
     const int zl = plane0 + pz;
 #ifdef ZD_STAMPS
     if (zd_stamps && threadIdx.x == 0) {
@@ -1497,6 +1506,7 @@ __device__ __forceinline__ void yfft_f_unit_t(const FieldLayout &F, const StoreL
     // double(kx^2 + ky^2) * fund2 >= k2_cutoff is monotonic in the integer: c2 = the smallest integer that satisfies it
     unsigned skipm = 1u << ((N / 2 - t) / T);  // the Nyquist row y = N/2 is thread 0's (bit E/2; other threads: a bit they do not own)
     if (t != 0) skipm = 0;
+    if (PAIR && dline && x == 0) skipm = (1u << E) - 1u;  // the mirror slot of column 0 stands for column N/2: zeros
     if (S.prune & 4) {
         int c2 = 0x7fffffff;
         if (S.k2_cutoff > 0) {
@@ -1562,8 +1572,14 @@ __device__ __forceinline__ void yfft_f_unit_t(const FieldLayout &F, const StoreL
                 const double s = y > N / 2 ? -1.0 : 1.0;
                 const double ur = re[e], ui = im[e];
                 const bool skip = (skipm >> e) & 1u;
-                re[e] = skip ? 0.0 : -ui - s * v[j].x;
-                im[e] = skip ? 0.0 : s * ur - v[j].y;
+                if constexpr (PAIR) {  // D line: i U0 + U1, the v terms with the opposite sign
+                    const double vx = dline ? -v[j].x : v[j].x, vy = dline ? -v[j].y : v[j].y;
+                    re[e] = skip ? 0.0 : -ui - s * vx;
+                    im[e] = skip ? 0.0 : s * ur - vy;
+                } else {
+                    re[e] = skip ? 0.0 : -ui - s * v[j].x;
+                    im[e] = skip ? 0.0 : s * ur - v[j].y;
+                }
             }
         }
     } else {  // u = E_r:  (i kx - ky) u,  mirrored (i kx + (N - y)) conj u
@@ -1574,11 +1590,20 @@ __device__ __forceinline__ void yfft_f_unit_t(const FieldLayout &F, const StoreL
         for (int e = 0; e < E; e++) {
             const int y = tc + T * e;
             const bool mir = y > N / 2;
-            const double s = mir ? -1.0 : 1.0, dky = (double) (mir ? N - y : y);
-            const double ur = re[e], ui = im[e];
-            const bool skip = (skipm >> e) & 1u;
-            re[e] = skip ? 0.0 : -s * (dky * ur + dkx * ui);
-            im[e] = skip ? 0.0 : dkx * ur - dky * ui;
+            if constexpr (PAIR) {  // D line: (i kx + ky) U, ky with the opposite sign
+                const int iky = mir ? N - y : y;
+                const double s = mir ? -1.0 : 1.0, dky = (double) (dline ? -iky : iky);
+                const double ur = re[e], ui = im[e];
+                const bool skip = (skipm >> e) & 1u;
+                re[e] = skip ? 0.0 : -s * (dky * ur + dkx * ui);
+                im[e] = skip ? 0.0 : dkx * ur - dky * ui;
+            } else {
+                const double s = mir ? -1.0 : 1.0, dky = (double) (mir ? N - y : y);
+                const double ur = re[e], ui = im[e];
+                const bool skip = (skipm >> e) & 1u;
+                re[e] = skip ? 0.0 : -s * (dky * ur + dkx * ui);
+                im[e] = skip ? 0.0 : dkx * ur - dky * ui;
+            }
         }
     }
     if (ZD_TUNE(S.prune & 4096) && a == 2) return;                           // bit 12: tuning ablation (no x array)
@@ -1587,7 +1612,7 @@ __device__ __forceinline__ void yfft_f_unit_t(const FieldLayout &F, const StoreL
     ZD_STAMP(3, unit, false);  // transformed
     if (ZD_TUNE(S.prune & 256) && re[0] != 123.456) return;                    // bit 8: tuning ablation (no stores)
     char *base = reinterpret_cast<char *>(ring + ((long long) (pz * 3 + a) * N) * ring_pitch);
-    const unsigned xb = (unsigned) x * 16u, pb = (unsigned) ring_pitch * 16u;
+    const unsigned xb = (unsigned) (PAIR ? tile * W + w : x) * 16u, pb = (unsigned) ring_pitch * 16u;
     int t2 = t;
     asm volatile("" : "+v"(t2));
 #pragma unroll
@@ -1597,24 +1622,24 @@ __device__ __forceinline__ void yfft_f_unit_t(const FieldLayout &F, const StoreL
         if constexpr (N > 8192)  // one array plane of the ring exceeds 4 GB
             *reinterpret_cast<cplx *>(base + ((size_t) slot * pb + xb)) = cplx{re[e], im[e]};
         else
-            st_stream(reinterpret_cast<cplx *>(base + (slot * pb + xb)), cplx{re[e], im[e]}, ZD_NTBIT(S, 32));
+            st_stream(reinterpret_cast<cplx *>(base + (slot * pb + xb)), cplx{re[e], (PAIR && dline) ? -im[e] : im[e]}, ZD_NTBIT(S, 32));
     }
     ZD_STAMP(4, unit, false);  // stores issued
     ZD_STAMP(5, unit, true);   // stores acknowledged (wave 0's)
 }
 //   grid: (3*N/W, 1, planes)   block: W*N/E
-template <int N, int E, int W, int MINW = 1>
+template <int N, int E, int W, int MINW = 1, bool PAIR = false>
 __global__ __launch_bounds__(W *N / E, MINW) void k_yfft_f(FieldLayout F, StoreLayout S, const cplx *__restrict__ tw,
                                                           const cplx *__restrict__ store, int plane0, int ring_pitch,
                                                           cplx *__restrict__ ring) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    yfft_f_unit<N, E, W>(F, S, tw, store, plane0, ring_pitch, ring, (int) blockIdx.x, (int) blockIdx.z, (int) threadIdx.x / W,
+    yfft_f_unit<N, E, W, PAIR>(F, S, tw, store, plane0, ring_pitch, ring, (int) blockIdx.x, (int) blockIdx.z, (int) threadIdx.x / W,
                          (int) threadIdx.x % W, lds);
 }
 // Persistent form: gridDim.x workgroups (a multiple of 8, so that a workgroup keeps its XCD class = linear index mod 8) walk
 // the (plane, workgroup index) list with stride gridDim.x: the ring stores of one unit and the potential loads of the next
 // are in flight together (as separate workgroups filling the CU, the next one's loads wait for the previous one's stores).
-template <int N, int E, int W, int MINW = 1>
+template <int N, int E, int W, int MINW = 1, bool PAIR = false>
 __global__ __launch_bounds__(W *N / E, MINW) void k_yfft_fp(FieldLayout F, StoreLayout S, const cplx *__restrict__ tw,
                                                            const cplx *__restrict__ store, int plane0, int ring_pitch,
                                                            cplx *__restrict__ ring, int nplanes) {
@@ -1625,7 +1650,7 @@ __global__ __launch_bounds__(W *N / E, MINW) void k_yfft_fp(FieldLayout F, Store
     for (int work = blockIdx.x; work < nwork; work += gridDim.x) {
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));  // per-iteration value: nothing that depends on the thread index is hoisted (and spilled)
-        yfft_f_unit<N, E, W>(F, S, tw, store, plane0, ring_pitch, ring, work % PER, work / PER, tid / W, tid % W, lds);
+        yfft_f_unit<N, E, W, PAIR>(F, S, tw, store, plane0, ring_pitch, ring, work % PER, work / PER, tid / W, tid % W, lds);
     }
 }
 
@@ -1856,8 +1881,9 @@ __global__ __launch_bounds__(ROWS *NA *N / E, (ROWS * NA * N / E == 512 ? 4 : 1)
 // (qx + i qy)_r0 | (qx + i qy)_r1 | qz_r0 + i qz_r1, so the two delivered planes need {array 0, Re array 2} and
 // {array 1, Im array 2}: array 2 is transformed first and kept in registers, then each of the other two is transformed
 // and its plane's records are written at once — never more than two arrays' results are live.
+// PW > 0: the ring's rows are paired in groups of PW elements (zd_device.h ring_pair_w): position p holds column ring_pair_col(p).
 //   grid: (N, nplanes)   block: N/E
-template <int N, int E>
+template <int N, int E, int PW = 0>
 __global__ __launch_bounds__(N / E, 2) void k_xfft_seq(StoreLayout S, EpiConst ec, const cplx *__restrict__ tw,
                                                    const cplx *__restrict__ data, int plane0, int z_first, int z_step,
                                                    char *__restrict__ records, Reduce *__restrict__ red) {
@@ -1884,9 +1910,14 @@ __global__ __launch_bounds__(N / E, 2) void k_xfft_seq(StoreLayout S, EpiConst e
         double re[E], im[E];
         int ta = t;
         asm volatile("" : "+v"(ta));
+        // PW: the loads go by POSITION, whole lines per wave as on plain rows; thread t then holds the columns ring_pair_col(t + T e) and
+        // hands them over through the transform's own LDS area, re and then im, written at the column and read back in the transform's
+        // layout (four more barriers per array, no more LDS).  (Loading column t + T e from its position directly — a lane pair reads
+        // 32 of every 64 bytes, the requests to the L1 double — cost the x stage 50-60 ms per step at PPD = 4096: profiles/CHANGELOG.md.)
 #pragma unroll
         for (int e = 0; e < E; e++) {
-            const cplx v = src[x_is_dead(ec, ta + T * e) ? 0 : ta + T * e];  // (see k_xfft)
+            const int xe = PW ? ring_pair_col(N, PW, ta + T * e) : ta + T * e;
+            const cplx v = src[x_is_dead(ec, xe) ? 0 : ta + T * e];  // (see k_xfft)
             re[e] = v.x;
             im[e] = v.y;
         }
@@ -1894,8 +1925,24 @@ __global__ __launch_bounds__(N / E, 2) void k_xfft_seq(StoreLayout S, EpiConst e
         asm volatile("" : "+v"(t3));  // the dead flags are recomputed behind the loads rather than kept beside them (registers)
 #pragma unroll
         for (int e = 0; e < E; e++)
-            if (x_is_dead(ec, t3 + T * e)) re[e] = im[e] = 0.0;
+            if (x_is_dead(ec, PW ? ring_pair_col(N, PW, t3 + T * e) : t3 + T * e)) re[e] = im[e] = 0.0;
         __syncthreads();  // the previous transform's last LDS reads are done
+        if constexpr (PW != 0) {
+            int tb = t;
+            asm volatile("" : "+v"(tb));
+#pragma unroll
+            for (int e = 0; e < E; e++) lds[LDS::idx(ring_pair_col(N, PW, tb + T * e), 0)] = re[e];
+            __syncthreads();
+            zdfft::xchg_read<PL, LDS>(re, t, 0, lds);
+            __syncthreads();
+            int tc = t;
+            asm volatile("" : "+v"(tc));
+#pragma unroll
+            for (int e = 0; e < E; e++) lds[LDS::idx(ring_pair_col(N, PW, tc + T * e), 0)] = im[e];
+            __syncthreads();
+            zdfft::xchg_read<PL, LDS>(im, t, 0, lds);
+            __syncthreads();
+        }
         zdfft::fft_line<PL, LDS>(re, im, t, 0, lds, tw);
         int t2 = t;
         asm volatile("" : "+v"(t2));
@@ -2742,7 +2789,7 @@ int launch_zfft_fields(int L, const FieldLayout &F, const StoreLayout &S, int ky
     return 2;
 }
 
-template <int N, int E, int W, bool PERSIST = false, int MINW = 1>
+template <int N, int E, int W, bool PERSIST = false, int MINW = 1, bool PAIR = false>
 static int launch_yfft_f_t(const FieldLayout &F, const StoreLayout &S, const void *tw, const void *store, int plane0,
                            int nplanes, int ring_pitch, void *ring, hipStream_t st) {
     constexpr int threads = W * N / E;
@@ -2756,19 +2803,19 @@ static int launch_yfft_f_t(const FieldLayout &F, const StoreLayout &S, const voi
     }
     ZD_PROBE_RETURN();
     if constexpr (PERSIST) {
-        set_dyn_lds<k_yfft_fp<N, E, W, MINW>>(shmem_max);
+        set_dyn_lds<k_yfft_fp<N, E, W, MINW, PAIR>>(shmem_max);
         int dev = 0, ncu = 256;
         hipGetDevice(&dev);
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
         const int per_cu = std::max(1, std::min((int) (160 * 1024 / shmem), 2048 / (threads * (MINW > 1 ? 1 : 2))));
         dim3 grid((unsigned) std::max(8, ncu * per_cu / 8 * 8)), block(threads);
-        hipLaunchKernelGGL((k_yfft_fp<N, E, W, MINW>), grid, block, shmem, st, F, S, (const cplx *) tw, (const cplx *) store, plane0,
+        hipLaunchKernelGGL((k_yfft_fp<N, E, W, MINW, PAIR>), grid, block, shmem, st, F, S, (const cplx *) tw, (const cplx *) store, plane0,
                            ring_pitch, (cplx *) ring, nplanes);
         ZD_LAUNCH_CHECK();
     } else {
-        set_dyn_lds<k_yfft_f<N, E, W, MINW>>(shmem_max);
+        set_dyn_lds<k_yfft_f<N, E, W, MINW, PAIR>>(shmem_max);
         dim3 grid(3 * (N / W), 1, nplanes), block(threads);
-        hipLaunchKernelGGL((k_yfft_f<N, E, W, MINW>), grid, block, shmem, st, F, S, (const cplx *) tw, (const cplx *) store, plane0,
+        hipLaunchKernelGGL((k_yfft_f<N, E, W, MINW, PAIR>), grid, block, shmem, st, F, S, (const cplx *) tw, (const cplx *) store, plane0,
                            ring_pitch, (cplx *) ring);
     }
     ZD_LAUNCH_CHECK();
@@ -2777,10 +2824,23 @@ static int launch_yfft_f_t(const FieldLayout &F, const StoreLayout &S, const voi
 // y stage of the field store: store planes [plane0, plane0 + nplanes) -> ring planes [0, nplanes)
 int launch_yfft_fields(const FieldLayout &F, const StoreLayout &S, const void *tw, const void *store, int plane0,
                        int nplanes, int ring_pitch, void *ring, hipStream_t st) {
-#define YCASE(n, e, w) \
-    case n: return launch_yfft_f_t<n, e, w>(F, S, tw, store, plane0, nplanes, ring_pitch, ring, st);
+    // S.paired (the ring has paired rows: the ZA field store at the sizes of ring_pair_w): the pair form of the same tile shape
+#define YCASE(n, e, w)                                                                                                               \
+    case n:                                                                                                                          \
+        if constexpr (ring_pair_w(n) == w)                                                                                           \
+            if (S.paired == w) return launch_yfft_f_t<n, e, w, false, 1, true>(F, S, tw, store, plane0, nplanes, ring_pitch, ring, st); \
+        return launch_yfft_f_t<n, e, w>(F, S, tw, store, plane0, nplanes, ring_pitch, ring, st);
+    if (S.paired && (F.nfield != 4 || S.paired != ring_pair_w(S.N))) {
+#ifdef ZD_TESTING
+        // two pairs per workgroup (W = 4, otherwise only PPD = 4096) at a size a test can afford: zd_test_ring_pair_w
+        if (F.nfield == 4 && S.N == 1024 && S.paired == 4)
+            return launch_yfft_f_t<1024, 16, 4, false, 1, true>(F, S, tw, store, plane0, nplanes, ring_pitch, ring, st);
+#endif
+        ZD_TABLE_MISS("zeldovich_hip: no y stage for paired ring rows of %d at PPD %d\n", S.paired, S.N);
+        return 2;
+    }
 #ifdef ZD_TUNING
-    {
+    if (!S.paired) {  // (the A/B forms below write plain rows)
         const int yw = getenv("ZD_YW") ? atoi(getenv("ZD_YW")) : 0, yp = getenv("ZD_YPERSIST") ? atoi(getenv("ZD_YPERSIST")) : 0;
         if (S.N == 4096 && yw == 2 && !yp) return launch_yfft_f_t<4096, 16, 2, false, 4>(F, S, tw, store, plane0, nplanes, ring_pitch, ring, st);
         if (S.N == 4096 && yw == 2 && yp) return launch_yfft_f_t<4096, 16, 2, true, 4>(F, S, tw, store, plane0, nplanes, ring_pitch, ring, st);
@@ -2859,14 +2919,14 @@ static int launch_xfft_t(const StoreLayout &S, const EpiConst &ec, const void *t
     ZD_LAUNCH_CHECK();
     return 0;
 }
-template <int N, int E>
+template <int N, int E, int PW = 0>
 static int launch_xfft_seq_t(const StoreLayout &S, const EpiConst &ec, const void *tw, const void *data, int plane0,
                              int nplanes, int z_first, int z_step, void *records, Reduce *red, hipStream_t st) {
     const size_t shmem = sizeof(double) * (zdfft::LineInner<N, 1>::SIZE + N);  // + Im of array 2 (k_xfft_seq)
     ZD_PROBE_RETURN();
-    set_dyn_lds<k_xfft_seq<N, E>>(shmem);
+    set_dyn_lds<k_xfft_seq<N, E, PW>>(shmem);
     dim3 grid(N, nplanes), block(N / E);
-    hipLaunchKernelGGL((k_xfft_seq<N, E>), grid, block, shmem, st, S, ec, (const cplx *) tw, (const cplx *) data, plane0, z_first,
+    hipLaunchKernelGGL((k_xfft_seq<N, E, PW>), grid, block, shmem, st, S, ec, (const cplx *) tw, (const cplx *) data, plane0, z_first,
                        z_step, (char *) records, red);
     ZD_LAUNCH_CHECK();
     return 0;
@@ -2929,6 +2989,21 @@ static int launch_xfft_two_t(const StoreLayout &S, const EpiConst &ec, const voi
     return 0;
 }
 
+// k_xfft_seq on the ring of the ZA field store at a size of ring_pair_w: plain or paired rows (StoreLayout::paired)
+template <int N>
+static int xfft_seq_ring(const StoreLayout &S, const EpiConst &ec, const void *tw, const void *data, int plane0, int nplanes, int z_first,
+                         int z_step, void *records, Reduce *red, hipStream_t st) {
+    if (S.paired == ring_pair_w(N))
+        return launch_xfft_seq_t<N, 16, ring_pair_w(N)>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
+#ifdef ZD_TESTING
+    if constexpr (N == 1024)  // zd_test_ring_pair_w: see launch_yfft_fields
+        if (S.paired == 4) return launch_xfft_seq_t<N, 16, 4>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
+#endif
+    // (plain rows at these sizes: no plan lays the ZA ring out that way any more, so the form is not instantiated)
+    ZD_TABLE_MISS("zeldovich_hip: no x pass for ring rows paired by %d at PPD %d\n", S.paired, N);
+    return 2;
+}
+
 int launch_xfft(const StoreLayout &S, const EpiConst &ec, const void *tw, const void *data, int plane0, int nplanes,
                 int z_first, int z_step, void *records, float *density, Reduce *red, hipStream_t st) {
     if (S.lq) {  // plane-interleaved rows: the store of the fused PLT Z stage (zd_kernels_fz.hip)
@@ -2949,11 +3024,11 @@ int launch_xfft(const StoreLayout &S, const EpiConst &ec, const void *tw, const 
     // x stage 798 -> 713 ms (3.85 TB at 5.4 TB/s)
     // (8 elements per thread — 512 threads at 116 registers, twice the waves in the same two workgroups — is slower: 714 vs 699 ms)
     if (S.N == 4096 && S.narray == 3 && ec.pack == PACK_ZAFIELD)
-        return launch_xfft_seq_t<4096, 16>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
+        return xfft_seq_ring<4096>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
     if (S.N == 1024 && S.narray == 3 && ec.pack == PACK_ZAFIELD)  // one wave per workgroup: 13.5 -> 11.0 ms
-        return launch_xfft_seq_t<1024, 16>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
+        return xfft_seq_ring<1024>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
     if (S.N == 2048 && S.narray == 3 && ec.pack == PACK_ZAFIELD)  // 128 threads, four workgroups per CU: 101.6 -> 89.5 ms
-        return launch_xfft_seq_t<2048, 16>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
+        return xfft_seq_ring<2048>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
     if (S.N == 16384 && S.narray == 3 && ec.pack == PACK_ZAFIELD)
         return launch_xfft_two_t<16384, 16, false>(S, ec, tw, data, plane0, nplanes, z_first, z_step, records, red, st);
     if (S.N == 8192 && S.narray == 3 && ec.pack == PACK_PLT3)  // the ring of the PLT field store

@@ -49,6 +49,7 @@ inline bool has_xfft(int N, int narray, int pack, int lq, int one_block) {
     S.narray    = narray;
     S.lq        = lq;
     S.one_block = one_block;
+    S.paired    = pack == PACK_ZAFIELD && narray == 3 ? ring_pair_w(N) : 0;  // (the ring of the ZA potentials, as plan_store lays it out)
     EpiConst ec{};
     ec.N      = N;
     ec.narray = narray;

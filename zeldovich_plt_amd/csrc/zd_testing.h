@@ -53,6 +53,9 @@ int zd_test_fft(int32_t n, int64_t lines, int32_t axis_kind, const double *in, d
 int zd_test_ycols(int32_t n, int32_t G, int32_t ncols, int32_t nimg, int32_t mode, const double *in, double *out);
 /* on != 0: every store / exchange ring / phi field the library allocates from now on starts out as NaN bytes */
 void zd_test_poison(int on);
+/* w = 4: plans of the ZA field store at PPD = 1024 created from now on pair their ring rows in groups of 4 — two column pairs per y
+ * workgroup, the form PPD = 4096 runs — instead of 8 (zd_device.h ring_pair_w); 0: back to the table */
+void zd_test_ring_pair_w(int w);
 /* rank >= 0: that rank of the thread-per-GPU driver (zd_generate with ngpu > 1, zd_test_generate_loopback) fails BEFORE its first
  * pass — its peers are then blocked inside their first grouped send / receive, which only an abort ends; -1: nobody */
 void zd_test_fail_rank(int rank);
