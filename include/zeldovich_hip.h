@@ -432,6 +432,37 @@ typedef int (*zd_particle_cb)(void *user, int64_t first_particle, int64_t n, con
 int zd_displace(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t order, int64_t npart, const double *pos_xyz,
                 int64_t tile, int64_t max_particles_per_sweep, zd_particle_cb cb, void *user, zd_stats *out);
 
+/* ---- a caller-supplied density or white-noise field instead of ZD_Seed ---------------------------
+ * The phases of a run come from a field the caller hands over — a white-noise cube shared with another code, a constrained
+ * realisation, a field sampled by an inference chain, the density file an earlier ZD_qdensity = 1 run wrote — instead of the
+ * counter-addressed draws; the definition is pinned in csrc/zd_kernels_field.hip.
+ *   field     a real field a[z][y][x], ppd points per side, C-contiguous, float32 or float64 (dtype), a HOST pointer or, with
+ *             field_on_device != 0, a DEVICE pointer (read where it lies, not copied; a host field is uploaded in chunks of planes)
+ *   kind      ZD_FIELD_DENSITY: the linear density delta in the run's own units (what ZD_qdensity = 1 delivers):
+ *                 D(k) = (1 / ppd^3) sum_x a(x) exp(-2 pi i k.x / ppd)
+ *             ZD_FIELD_WHITE: unit-variance white noise: D(k) = W(k) sqrt(zd_pk_power(|k|) / ppd^3), W the unnormalised forward
+ *                 sum; with <|W|^2> = ppd^3 this is <|D|^2> = power(k), the variance of a seeded run
+ * D(k) is then cleared by the run's zero rule (src/zeldovich.cpp:350-356): the |k_i| = kmax planes, k^2 >= k^2_cutoff without
+ * ZD_CornerModes, ZD_qonemode, k = 0 — and the planes |k_i| = ppd/2, which the rule clears by itself unless ZD_CornerModes meets
+ * ZD_k_cutoff != 1.  With ZD_qdensity = 1 the density the run delivers is therefore the imposed field with those modes removed;
+ * displacements and velocities are what the path makes of these D(k), exactly as if the draws had produced them (eigenmode direction,
+ * f of the eigenvalue and the rescale under PLT, vnorm under ZA).  ZD_Seed is ignored; no draw is made.
+ * The intake (three transform stages of its own) holds D(k) of the half space, 8 ppd^3 bytes, which the plan then owns, plus a workspace
+ * of at most 256 MB (4 planes at ppd = 2048); the plan runs on the reference's arrays at any stream factor they take.
+ * zd_plan_create_field creates a one-rank plan: the stage calls, zd_plan_run_passes, zd_plan_stats, zd_plan_interp, zd_plan_direct_sum and
+ * zd_plan_measure_power work on it as on any plan.  zd_generate_field is the one-call form with zd_generate's callback.
+ * Accepted: ppd a power of two in [32, 2048], one GPU; ZA, ZD_qPLT with or without ZD_qPLT_rescale; every ICFormat; ZD_qdensity 0 / 1 / 2;
+ * ZD_k_cutoff, ZD_CornerModes, ZD_qonemode, ZD_f_cluster, ZD_qoneslab; any stream factor.  Refused before the GPU is touched, with one line
+ * that starts "zeldovich_hip: ZD_Field" and names the other option: ZD_f_NL != 0, ZD_q2LPT / ZD_q3LPT, ZD_Version = 1,
+ * ZD_qPk_fix_to_mean, ZD_NumGPU > 1, any other ppd, an unknown kind or dtype, a NULL field.  A job that does not fit is refused with
+ * the byte figure in the message. */
+enum { ZD_FIELD_DENSITY = 0, ZD_FIELD_WHITE = 1 };
+enum { ZD_FIELD_F32 = 0, ZD_FIELD_F64 = 1 };
+int zd_plan_create_field(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t kind, int32_t dtype,
+                         const void *field, int32_t field_on_device, zd_plan **out);
+int zd_generate_field(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t kind, int32_t dtype,
+                      const void *field, int32_t field_on_device, zd_slab_cb cb, void *user, zd_stats *out);
+
 /* ---- diagnostics ------------------------------------------------------------------------------
  * Which kernel variants this process has launched so far, and how often: one line "count<TAB>line<TAB>launcher" per launch
  * site of the library, the launcher named with its template arguments (transform length, elements per thread, tile shape,

@@ -92,6 +92,7 @@ EXPORTED_SYMBOLS = [
     "zd_plan_direct_sum", "zd_direct_sum", "zd_make_eigenmodes", "zd_write_eigmodes", "zd_param_file_string",
     "zd_plan_lpt_direct_sum", "zd_lpt_direct_sum", "zd_plan_lpt_power", "zd_lpt_power",
     "zd_interp_create", "zd_interp_add_plane", "zd_interp_result", "zd_interp_destroy", "zd_plan_interp", "zd_displace",
+    "zd_plan_create_field", "zd_generate_field",
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
@@ -216,6 +217,8 @@ def _load(path, testing):
     L.zd_interp_destroy.restype = None
     L.zd_plan_interp.argtypes = [vp, vp, vp]
     L.zd_displace.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i64, vp, i64, i64, PARTICLE_CB, vp, C.POINTER(ZdStats)]
+    L.zd_plan_create_field.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i32, vp, i32, C.POINTER(vp)]
+    L.zd_generate_field.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i32, vp, i32, SLAB_CB, vp, C.POINTER(ZdStats)]
     L.zd_dispatch_report.argtypes = [C.c_char_p, i64]
     L.zd_dispatch_report.restype = i64
     return L
@@ -370,12 +373,18 @@ def generate(params, ps, eig=None, collect=True, loopback=False, testing=False):
     emulation of its calls."""
     L = load_testing_library() if (loopback or testing) else load_library()  # testing: zd_generate of the -DZD_TESTING build (zd_test_poison)
     entry = L.zd_test_generate_loopback if loopback else L.zd_generate
-    n = int(params.ppd)
-    st = ZdStats()
     eigp, eig_ppd = (None, 0)
     if eig is not None:
         eig = np.ascontiguousarray(eig, dtype=np.float64)
         eigp, eig_ppd = eig.ctypes.data, eig.shape[0]
+    return _collecting_run(params, collect, lambda cb, st: entry(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, cb, None, C.byref(st)),
+                           "zd_generate")
+
+
+def _collecting_run(params, collect, call, what):
+    """call(cb, stats) -> rc with zd_generate's callback: gathers the delivered planes (collect) or runs the NULL sink"""
+    n = int(params.ppd)
+    st = ZdStats()
     out = {}
     if collect:
         dt = RECORD_DTYPES[_fmt_name(params.icformat)]
@@ -392,16 +401,62 @@ def generate(params, ps, eig=None, collect=True, loopback=False, testing=False):
             return 0
 
         cb = SLAB_CB(_cb)
-        rc = entry(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, cb, None, C.byref(st))
+        rc = call(cb, st)
         out["records"] = None if rec is None else rec.reshape(n, n, n)
         out["density"] = None if dens is None else dens.reshape(n, n, n)
         out["planes_seen"] = seen
     else:
-        rc = entry(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, SLAB_CB(), None, C.byref(st))
+        rc = call(SLAB_CB(), st)
     if rc:
-        raise RuntimeError("zd_generate failed (rc=%d); see stderr" % rc)
+        raise RuntimeError("%s failed (rc=%d); see stderr" % (what, rc))
     out.update(_stats_dict(st))
     return out
+
+
+FIELD_KINDS = {"density": 0, "white": 1}  # ZD_FIELD_DENSITY, ZD_FIELD_WHITE
+
+
+def _field_arg(field, ppd, kind):
+    """(kind code, dtype code, pointer, on_device) of a field handed to generate_field / Plan.from_field: a numpy array or a torch
+    tensor on the GPU, float32 or float64, of shape (ppd, ppd, ppd), C-contiguous.  Anything else raises before the library is called."""
+    if kind not in FIELD_KINDS:
+        raise ValueError("field kind must be one of %s (got %r)" % (sorted(FIELD_KINDS), kind))
+    n = int(ppd)
+    if isinstance(field, np.ndarray):
+        if field.dtype not in (np.float32, np.float64):
+            raise TypeError("field: float32 or float64 expected (got %s)" % field.dtype)
+        if field.shape != (n, n, n):
+            raise ValueError("field: shape (%d, %d, %d) expected (got %r)" % (n, n, n, field.shape))
+        if not field.flags["C_CONTIGUOUS"]:
+            raise ValueError("field: a C-contiguous array [z][y][x] expected")
+        return FIELD_KINDS[kind], int(field.dtype == np.float64), field.ctypes.data, 0
+    if type(field).__module__.split(".")[0] == "torch" and hasattr(field, "data_ptr"):
+        import torch
+        if not field.is_cuda:
+            raise ValueError("field: a torch tensor must live on the GPU (pass a numpy array for host data)")
+        if field.dtype not in (torch.float32, torch.float64):
+            raise TypeError("field: float32 or float64 expected (got %s)" % field.dtype)
+        if tuple(field.shape) != (n, n, n):
+            raise ValueError("field: shape (%d, %d, %d) expected (got %r)" % (n, n, n, tuple(field.shape)))
+        if not field.is_contiguous():
+            raise ValueError("field: a C-contiguous tensor [z][y][x] expected")
+        torch.cuda.synchronize(field.device)  # the library works on its own stream
+        return FIELD_KINDS[kind], int(field.dtype == torch.float64), field.data_ptr(), 1
+    raise TypeError("field: a numpy array or a torch tensor on the GPU expected (got %s)" % type(field).__name__)
+
+
+def generate_field(params, ps, field, kind="density", eig=None, collect=True):
+    """generate() with the modes taken from a caller-supplied real field instead of ZD_Seed (zd_generate_field; definition in
+    csrc/zd_kernels_field.hip).  field: numpy array or torch tensor on the GPU, float32 or float64, shape (ppd, ppd, ppd) = [z][y][x],
+    C-contiguous.  kind: "density" (the linear density in the run's units) or "white" (unit-variance white noise, coloured by ps)."""
+    kcode, dcode, ptr, on_device = _field_arg(field, params.ppd, kind)
+    L = load_library()
+    eigp, eig_ppd = (None, 0)
+    if eig is not None:
+        eig = np.ascontiguousarray(eig, dtype=np.float64)
+        eigp, eig_ppd = eig.ctypes.data, eig.shape[0]
+    return _collecting_run(params, collect, lambda cb, st: L.zd_generate_field(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, kcode, dcode,
+                                                                               ptr, on_device, cb, None, C.byref(st)), "zd_generate_field")
 
 
 PLT_MAX_PPD = 512  # ZD_PLT_MAX_PPD
@@ -662,15 +717,16 @@ def generate_planes(params, ps, on_plane, eig=None):
 class Plan:
     """Staged API: one rank's share of the Z and XY stages on device pointers (see the header)."""
 
-    def __init__(self, params, ps, eig=None, rank=0, nranks=1, testing=False):
+    def __init__(self, params, ps, eig=None, rank=0, nranks=1, testing=False, _field=None):
         self.L = load_testing_library() if testing else load_library()  # testing: the -DZD_TESTING build (zd_test_poison), tests only
         self.params = params
         self._eig = None if eig is None else np.ascontiguousarray(eig, dtype=np.float64)
         h = C.c_void_p()
-        rc = self.L.zd_plan_create(C.byref(params), C.byref(ps.pk),
-                                   None if self._eig is None else self._eig.ctypes.data,
-                                   0 if self._eig is None else self._eig.shape[0], rank, nranks, C.byref(h))
-        if rc:
+        eigp, eig_ppd = (None, 0) if self._eig is None else (self._eig.ctypes.data, self._eig.shape[0])
+        if _field is not None:  # from_field: (kind code, dtype code, pointer, on_device)
+            if self.L.zd_plan_create_field(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, *_field, C.byref(h)):
+                raise RuntimeError("zd_plan_create_field failed; see stderr")
+        elif self.L.zd_plan_create(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, rank, nranks, C.byref(h)):
             raise RuntimeError("zd_plan_create failed")
         self.h = h
         self.rank, self.nranks = rank, nranks
@@ -682,6 +738,12 @@ class Plan:
         self.record_size = self.L.zd_plan_record_size(h)
         self.exchange_bytes = self.L.zd_plan_exchange_bytes(h)
         self.local_planes = self.L.zd_plan_local_planes(h)
+
+    @classmethod
+    def from_field(cls, params, ps, field, kind="density", eig=None):
+        """a one-rank plan whose modes come from a caller-supplied real field (zd_plan_create_field; see generate_field): every
+        method of a plan works on it.  The field is consumed here: the plan keeps its modes, not the array."""
+        return cls(params, ps, eig=eig, _field=_field_arg(field, params.ppd, kind))
 
     def plane_z(self, residue, local_plane):
         return self.L.zd_plan_plane_z(self.h, residue, local_plane)

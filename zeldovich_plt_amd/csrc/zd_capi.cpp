@@ -645,7 +645,7 @@ static int any_lines(const zd_plan *pl, void *data, long long pitch, long long n
 // phi_mode 1: first f_NL pass (one array holding phi = D/M); phik != NULL: second pass (D = phik * M).  ZD_q2LPT: phi_mode 2 = the
 // plan of the second-order round's gradient passes; phik != NULL with phi_mode 0 = the final pass, phik holding the source S(k)
 static int plan_create_ex(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
-                          int phi_mode, const cplx *phik, PlanPtr &out);
+                          int phi_mode, const cplx *phik, PlanPtr &out, bool field = false);
 // a plan that was made goes to a caller of the C ABI; *out is left alone otherwise
 static int hand_over(int rc, PlanPtr &pl, zd_plan **out) {
     if (!rc) *out = pl.release();
@@ -702,6 +702,83 @@ static int make_phik(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d_phik) 
         if (zd::launch_fnl_stage(2, ph->S, p->f_NL, ph->d_twN, d_phi, d_out, (int) N, lN, 0)) return 1;
     }
     if (hipDeviceSynchronize() != hipSuccess) return 1;
+    d_phik = std::move(d_out);
+    return 0;
+}
+
+// ---- a caller-supplied density or white-noise field (definition and kernels: zd_kernels_field.hip) ----
+static void gen_zero_rule(zd::GenConst &g, const zd_params *p);
+struct FieldSpec {
+    int32_t kind, dtype;  // ZD_FIELD_DENSITY / _WHITE, ZD_FIELD_F32 / _F64
+    const void *field;    // a[z][y][x], C-contiguous
+    int32_t on_device;
+};
+// what a field run refuses, one line that starts "zeldovich_hip: ZD_Field" and names the other option; asked before the GPU is touched
+static int field_refused(const zd_params *p, const zd_pk *pk, const FieldSpec &f) {
+    char why[256] = "";
+    const int64_t N = p->ppd;
+    if (!f.field) snprintf(why, sizeof why, "no field given (NULL)");
+    else if (f.kind != ZD_FIELD_DENSITY && f.kind != ZD_FIELD_WHITE) snprintf(why, sizeof why, "kind = %d (ZD_FIELD_DENSITY or ZD_FIELD_WHITE expected)", f.kind);
+    else if (f.dtype != ZD_FIELD_F32 && f.dtype != ZD_FIELD_F64) snprintf(why, sizeof why, "dtype = %d (ZD_FIELD_F32 or ZD_FIELD_F64 expected)", f.dtype);
+    else if (p->f_NL != 0.) snprintf(why, sizeof why, "is not supported together with ZD_f_NL != 0 (the phi round makes PhiK from its own draws)");
+    else if (p->q2LPT || p->q3LPT || p->lpt2_dealias)
+        snprintf(why, sizeof why, "is not supported together with %s (its final pass keeps S(k) where PhiK goes)", p->q3LPT ? "ZD_q3LPT" : "ZD_q2LPT");
+    else if (p->version == 1) snprintf(why, sizeof why, "is not supported together with ZD_Version = 1 (a field run makes no draw; leave ZD_Version at 2)");
+    else if (pk->fixed_power) snprintf(why, sizeof why, "is not supported together with ZD_qPk_fix_to_mean (the amplitudes are the field's own)");
+    else if (p->ngpu > 1) snprintf(why, sizeof why, "runs on one GPU: ZD_NumGPU = %d", p->ngpu);
+    else if (!is_pow2(N) || N < 32 || N > 2048)
+        snprintf(why, sizeof why, "needs PPD a power of two in [32, 2048], got PPD = %lld (composite and convolution sizes: not yet)", (long long) N);
+    if (!why[0]) return 0;
+    fprintf(stderr, "zeldovich_hip: ZD_Field %s\n", why);
+    return 1;
+}
+// planes of the intake's workspace (complex x-stage output) and of the staging buffer of a host field: at least 4, at most 256 MB
+static int field_ws_planes(int64_t N) { return (int) std::min<int64_t>(N, std::max<int64_t>(4, ((int64_t) 1 << 28) / (N * N * 16))); }
+// The field -> d_phik = D(k)[ky][kz][x] for the half-space rows, zero rule and amplitude applied (owned by the caller, untouched on
+// failure).  PhiK is the only N^3-sized allocation; x and y stages run chunk by chunk through the workspace, a host field through a
+// staging buffer of as many planes; the z lines then run in place on PhiK.
+static int make_field_phik(const zd_params *p, const zd_pk *pk, const FieldSpec &f, DevBuf<cplx> &d_phik) {
+    const int64_t N = p->ppd, P = field_ws_planes(N), esz = f.dtype == ZD_FIELD_F32 ? 4 : 8;
+    const int64_t phik_b = fnl_phik_bytes(N), ws_b = P * N * N * 16, stage_b = f.on_device ? 0 : P * N * N * esz;
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+    DevBuf<cplx> d_out, d_ws, d_tw;
+    DevBuf<char> d_stage;
+    DevBuf<double> d_amp;
+    if (phik_b + ws_b + stage_b > (int64_t) free_b || d_out.store_alloc((size_t) (N / 2) * N * N) != hipSuccess
+        || d_ws.store_alloc((size_t) P * N * N) != hipSuccess || (stage_b && d_stage.alloc((size_t) stage_b) != hipSuccess)) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field needs %.2f GB of HBM for the modes of the field at PPD %lld (%.2f GB of them the workspace), %.2f GB are free\n",
+                (phik_b + ws_b + stage_b) / 1e9, (long long) N, (ws_b + stage_b) / 1e9, free_b / 1e9);
+        return 1;
+    }
+    zd::GenConst g;
+    gen_zero_rule(g, p);
+    {   // amp[|k|^2] over the integer |k|^2 the zero rule can leave alive: 1 / N^3, or sqrt(power(|k|) / N^3) for white noise
+        const long long all = 3LL * g.half * g.half + 1, n = std::max<long long>(1, g.corner_modes ? all : std::min<long long>(all, g.k2i_cut));
+        const double n3 = (double) N * (double) N * (double) N;
+        std::vector<double> amp((size_t) n, 1.0 / n3);
+        if (f.kind == ZD_FIELD_WHITE)
+            for (long long i = 1; i < n; i++) amp[(size_t) i] = sqrt(zd_pk_power(pk, sqrt((double) i * g.fundamental2)) / n3);
+        amp[0] = 0.0;
+        HIPCHECK(upload(d_amp, amp));
+    }
+    HIPCHECK(upload(d_tw, make_twiddles((int) N)));
+    const hipStream_t st = 0;
+    for (int64_t z0 = 0; z0 < N; z0 += P) {
+        const int np = (int) std::min<int64_t>(P, N - z0);
+        const char *src = (const char *) f.field + (size_t) z0 * N * N * esz;
+        if (!f.on_device) {  // (the copy returns when the planes are staged; the kernels of the chunk before are ordered before it)
+            HIPCHECK(hipMemcpyAsync(d_stage, src, (size_t) np * N * N * esz, hipMemcpyHostToDevice, st));
+            src = d_stage;
+        }
+        if (zd::launch_field_x((int) N, src, f.dtype == ZD_FIELD_F32, d_tw, d_ws, np, st)) return 1;
+        if (zd::launch_field_y((int) N, d_tw, d_ws, (int) z0, np, d_out, st)) return 1;
+    }
+    if (zd::launch_field_z(g, d_tw, d_amp, d_out, st)) return 1;
+    if (hipStreamSynchronize(st) != hipSuccess) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field: the intake failed: %s\n", hipGetErrorString(hipGetLastError()));
+        return 1;
+    }
     d_phik = std::move(d_out);
     return 0;
 }
@@ -1040,7 +1117,11 @@ static int plan_device_tables(zd_plan *pl, const zd_pk *pk, const double *eig, i
             g.pk_tab = (const double2 *) pl->d_pktab.get();
         }
     }
-    if (g.gen_phi || g.phik) {  // M(k) = 2 g c^2 T(k) k^2 / (3 Omega_M H0^2), zeldovich.cpp:377-383
+    if (pl->field) {  // a caller-supplied field: PhiK holds D itself, and ph * 1.0 is ph bit for bit
+        const std::vector<double> ones((size_t) (3LL * pl->half * pl->half + 2), 1.0);
+        HIPCHECK(upload(pl->d_fnlM, ones));
+        g.fnl_M = pl->d_fnlM;
+    } else if (g.gen_phi || g.phik) {  // M(k) = 2 g c^2 T(k) k^2 / (3 Omega_M H0^2), zeldovich.cpp:377-383
         const double H0 = 100., c = 299792.458, growth = 1. / (1 + p->z_initial);
         g.fnl_pre = 2. * growth * c * c;
         g.fnl_den = 3. * p->Omega_M * H0 * H0;
@@ -1419,12 +1500,34 @@ static int plan_slabs(zd_plan *pl, bool v1, int64_t eig_ppd) {
     return 0;
 }
 
+// a zeroed GenConst with the constants of the zero rule (zeldovich.cpp:299-320, 350; zd_device.h mode_is_zero): what every plan starts
+// from, and all that the intake of a caller-supplied field (make_field_phik) needs of it
+static void gen_zero_rule(zd::GenConst &g, const zd_params *p) {
+    memset(&g, 0, sizeof(g));
+    g.N            = (int) p->ppd;
+    g.half         = g.N / 2;
+    g.kmax         = (int) ((double) g.half * (1.0 / p->k_cutoff) + .5);
+    g.corner_modes = p->corner_modes;
+    g.qonemode     = p->qonemode;
+    for (int i = 0; i < 3; i++) g.one_mode[i] = p->one_mode[i];
+    g.fundamental  = p->fundamental;
+    g.fundamental2 = p->fundamental * p->fundamental;
+    g.k2_cutoff    = p->nyquist * p->nyquist / (p->k_cutoff * p->k_cutoff);
+    {  // the comparison `k2 >= k2_cutoff` of zeldovich.cpp:353 is monotonic in the integer |k|^2
+        long long c = (long long) floor(g.k2_cutoff / g.fundamental2);
+        while (c > 0 && (double) c * g.fundamental2 >= g.k2_cutoff) c--;
+        while ((double) c * g.fundamental2 < g.k2_cutoff) c++;
+        g.k2i_cut = (int) std::min<long long>(c, 0x7fffffffLL);
+    }
+}
+
 // a plan of the shape an accepted route gives; each part above fills its own members; a plan that fails half-way releases what it has
 static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
-                           int role, const cplx *phik, PlanPtr &out) {
+                           int role, const cplx *phik, bool field, PlanPtr &out) {
     PlanPtr plan(new zd_plan);
     zd_plan *pl   = plan.get();
     pl->p         = *p;
+    pl->field     = field;
     pl->rank      = rank;
     pl->nranks    = nranks;
     pl->N         = (int) p->ppd;
@@ -1443,23 +1546,8 @@ static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk,
     const bool v1 = p->version == 1 && phik == nullptr && !p->q2LPT;  // (the second f_NL pass takes D from PhiK and draws nothing)
     // ---- generator constants (zeldovich.cpp:299-320, 350) ----
     zd::GenConst &g = pl->g;
-    memset(&g, 0, sizeof(g));
-    g.N            = pl->N;
-    g.half         = pl->half;
-    g.kmax         = (int) ((double) pl->half * (1.0 / p->k_cutoff) + .5);
-    g.corner_modes = p->corner_modes;
+    gen_zero_rule(g, p);
     g.ablate       = tune_env("ZD_ABLATE") ? atoi(tune_env("ZD_ABLATE")) : 0;
-    g.qonemode     = p->qonemode;
-    for (int i = 0; i < 3; i++) g.one_mode[i] = p->one_mode[i];
-    g.fundamental  = p->fundamental;
-    g.fundamental2 = p->fundamental * p->fundamental;
-    g.k2_cutoff    = p->nyquist * p->nyquist / (p->k_cutoff * p->k_cutoff);
-    {  // the comparison `k2 >= k2_cutoff` of zeldovich.cpp:353 is monotonic in the integer |k|^2
-        long long c = (long long) floor(g.k2_cutoff / g.fundamental2);
-        while (c > 0 && (double) c * g.fundamental2 >= g.k2_cutoff) c--;
-        while ((double) c * g.fundamental2 < g.k2_cutoff) c++;
-        g.k2i_cut = (int) std::min<long long>(c, 0x7fffffffLL);
-    }
     g.pk_n         = pk->n;
     g.fixed_power  = pk->fixed_power;
     g.is_powerlaw  = pk->is_powerlaw;
@@ -1502,7 +1590,7 @@ static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk,
 }
 
 static int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
-                          int phi_mode, const cplx *phik, PlanPtr &out) {
+                          int phi_mode, const cplx *phik, PlanPtr &out, bool field) {
     const zd_params pc = zd::canonical(p_in);
     const int role = phi_mode == 1 ? zd::ROLE_PHI : phi_mode == 2 ? zd::ROLE_LPT2_GRAD : (phik && !pc.q2LPT) ? zd::ROLE_PHIK : zd::ROLE_MAIN;
     if (pc.q2LPT && role == zd::ROLE_MAIN && !phik) {  // (zd_plan_create and zd_generate run the second-order round first)
@@ -1515,8 +1603,8 @@ static int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *
     if (role == zd::ROLE_MAIN && zd::plt_dens_split(&pc, nranks) && have_eig && split_routes(&pc, pc.stream_factor, &pa, &pb, &ra, &rb) && ra.ok()
         && rb.ok()) {
         PlanPtr A, B;
-        if (plan_create_one(&pa, ra, pk, eig, eig_ppd, rank, nranks, role, nullptr, A) == 0
-            && plan_create_one(&pb, rb, pk, nullptr, 0, rank, nranks, role, nullptr, B) == 0
+        if (plan_create_one(&pa, ra, pk, eig, eig_ppd, rank, nranks, role, nullptr, false, A) == 0
+            && plan_create_one(&pb, rb, pk, nullptr, 0, rank, nranks, role, nullptr, false, B) == 0
             && A->d_dens_pass.store_alloc((size_t) A->Zq * pc.ppd * pc.ppd) == hipSuccess) {
             A->p            = pc;  // (what the callers read back: ZD_qdensity = 1)
             A->store_bytes_ = std::max(A->store_bytes_, B->store_bytes_);
@@ -1531,7 +1619,7 @@ static int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *
         fprintf(stderr, "zeldovich_hip: %s\n", rt.why);
         return 1;
     }
-    return plan_create_one(&pc, rt, pk, eig, eig_ppd, rank, nranks, role, phik, out);
+    return plan_create_one(&pc, rt, pk, eig, eig_ppd, rank, nranks, role, phik, field, out);
 }
 
 zd_plan::~zd_plan() {  // the members release themselves afterwards
@@ -1959,8 +2047,42 @@ int zd_plan_stats(zd_plan *pl, zd_stats *out) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// zd_generate, and zd_generate_field (fs != NULL: the modes come from the caller's field; its refusals have been asked)
+static int generate_impl(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, zd_slab_cb cb, void *user, zd_stats *out,
+                         const FieldSpec *fs);
 int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, zd_slab_cb cb,
                 void *user, zd_stats *out) {
+    return generate_impl(p_in, pk, eig, eig_ppd, cb, user, out, nullptr);
+}
+int zd_generate_field(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t kind, int32_t dtype, const void *field,
+                      int32_t field_on_device, zd_slab_cb cb, void *user, zd_stats *out) {
+    if (!p || !pk || !out) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field: zd_generate_field needs parameters, a power spectrum and a zd_stats\n");
+        return 1;
+    }
+    const FieldSpec fs{kind, dtype, field, field_on_device};
+    if (field_refused(p, pk, fs)) return 1;
+    return generate_impl(p, pk, eig, eig_ppd, cb, user, out, &fs);
+}
+int zd_plan_create_field(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t kind, int32_t dtype, const void *field,
+                         int32_t field_on_device, zd_plan **out) {
+    if (!p || !pk || !out) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field: zd_plan_create_field needs parameters, a power spectrum and a place for the plan\n");
+        return 1;
+    }
+    const FieldSpec fs{kind, dtype, field, field_on_device};
+    if (field_refused(p, pk, fs)) return 1;
+    DevBuf<cplx> d_phik;
+    if (make_field_phik(p, pk, fs, d_phik)) return 1;
+    PlanPtr pl;
+    if (plan_create_ex(p, pk, eig, eig_ppd, 0, 1, 0, d_phik, pl, true)) return 1;
+    pl->d_phik_owned = std::move(d_phik);
+    *out             = pl.release();
+    return 0;
+}
+
+static int generate_impl(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, zd_slab_cb cb, void *user, zd_stats *out,
+                         const FieldSpec *fs) {
     // ZD_NumGPU: one host thread per GPU, exchange inside the library (zd_multi.cpp).  (ZD_qoneslab finishes ONE plane of one
     // pass and reports the reductions of that slab alone, output.cpp:197: that is this single-GPU path's job.)
     if ((p_in->q2LPT || p_in->lpt2_dealias || p_in->q3LPT) && lpt2_route_check(p_in, p_in->ngpu > 1 ? p_in->ngpu : 1, 0)) return 1;
@@ -1978,8 +2100,13 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
     if (p.q2LPT && p.lpt2_dealias && !lpt2_round_fits(&p, (int64_t) free_b - ((int64_t) 16 << 30))) return 1;
     if (p.stream_factor <= 0) {
         // leave 16 GB for tables, the folded-input slabs (~3 GB), the record ring (8 GB) and the runtime
-        const int64_t budget = (int64_t) free_b - ((int64_t) 16 << 30);
-        const int R = zd_choose_stream_factor(&p, 1, budget);
+        int64_t budget = (int64_t) free_b - ((int64_t) 16 << 30);
+        zd_params pq = p;
+        if (fs) {  // a PhiK plan runs on the reference's arrays, beside PhiK (the intake's workspace is gone by then)
+            pq.store_mode = ZD_STORE_REFERENCE;
+            budget -= fnl_phik_bytes(N);
+        }
+        const int R = zd_choose_stream_factor(&pq, 1, budget);
         if (R < 0) {
             fprintf(stderr, "zeldovich_hip: PPD %lld does not fit in %.1f GB of free HBM at any stream factor\n",
                     (long long) N, free_b / 1e9);
@@ -2004,8 +2131,10 @@ int zd_generate(const zd_params *p_in, const zd_pk *pk, const double *eig, int64
     // ---- ZD_q3LPT: the third-order round (zd_kernels_lpt3.hip); P3(k) and C_x,y,z(k) stay beside S(k), counted likewise ----
     DevBuf<cplx> d_lpt3[4];
     if (p.q3LPT && make_lpt3_sources(&p, pk, d_phik, d_lpt3)) return 1;
+    // ---- a caller-supplied field (zd_kernels_field.hip): PhiK = its modes; no draw is made ----
+    if (fs && make_field_phik(&p, pk, *fs, d_phik)) return 1;
     PlanPtr plan;
-    if (plan_create_ex(&p, pk, eig, eig_ppd, 0, 1, 0, d_phik, plan)) return 1;
+    if (plan_create_ex(&p, pk, eig, eig_ppd, 0, 1, 0, d_phik, plan, fs != nullptr)) return 1;
     zd_plan *pl      = plan.get();
     pl->d_phik_owned = std::move(d_phik);
     if (p.q3LPT) adopt_lpt3(pl, d_lpt3);

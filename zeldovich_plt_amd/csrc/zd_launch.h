@@ -175,6 +175,13 @@ int launch_lpt3_xpair(const StoreLayout &S, const void *tw, const void *data, do
 int launch_lpt3_point(const Lpt3Fields &F, double g3a, double g3b, long long nsites, hipStream_t st);
 // rows of the real field src[z][y][x] / N^3 through the forward x transform into the one-array store (launch_fnl_stage 1, 2 go on)
 int launch_lpt3_xfwd(const StoreLayout &S, const void *tw, const double *src, void *data, int nplanes, hipStream_t st);
+// ---- intake of a caller-supplied real field (zd_kernels_field.hip): a[z][y][x] -> PhiK[ky < N/2][kz][x] ----
+// rows of the planes [0, nplanes) of src (float32 or float64, [plane][y][x]) through the x lines into work[plane][y][x] (complex)
+int launch_field_x(int N, const void *src, int is_f32, const void *tw, void *work, int nplanes, hipStream_t st);
+// y lines of those planes; the outputs ky < N/2 into phik[ky][z0 + plane][x]
+int launch_field_y(int N, const void *tw, const void *work, int z0, int nplanes, void *phik, hipStream_t st);
+// z lines of phik in place; the store conjugates, applies the zero rule of g and multiplies by amp[kx^2 + ky^2 + kz^2]
+int launch_field_z(const GenConst &g, const void *tw, const double *amp, void *phik, hipStream_t st);
 // ---- ZD_Version = 1 streams (zd_kernels_v1.hip) ----
 int launch_v1_seed(unsigned long long seed, int block, V1Stream *streams, hipStream_t st);
 int launch_v1_draw(const GenConst &g, int block, int ky0, int ky_stride, int nrows, V1Stream *streams, void *dev, int *err,

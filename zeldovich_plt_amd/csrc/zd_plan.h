@@ -87,6 +87,7 @@ struct zd_plan {
     zdown::DevBuf<double2> d_v1dev;     // [slab row][z][x]
     zdown::DevBuf<int> d_v1err;
     zdown::DevBuf<zdfft::cplx> d_phik_owned;  // ZD_f_NL: PhiK of the phi round; ZD_q2LPT: the source S(k) — whoever ran the round hands it over
+    bool field = false;  // PhiK is a caller-supplied field (zd_plan_create_field): D = PhiK itself, d_fnlM a table of ones
     zdown::DevBuf<zdfft::cplx> d_lpt3_owned[4];  // ZD_q3LPT: P3(k), C_x(k), C_y(k), C_z(k) of the third-order round, handed over likewise
     // any even PPD (zd_kernels_any.hip): Bluestein tables for the lengths L (z lines) and N (y, x lines)
     bool any = false;

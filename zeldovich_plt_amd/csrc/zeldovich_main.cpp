@@ -8,6 +8,7 @@
 // (DISK mode is replaced by HBM residency + z-residue streaming), planes may be produced out of z
 // order and are therefore placed with pwrite at their final offset instead of being appended.
 #include <fcntl.h>
+#include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -465,6 +466,60 @@ static int glass_run(const GlassKeys &gk, const zd_params &p, const zd_param_str
     return 0;
 }
 
+// ZD_Field_filename, ZD_Field_kind (optional, not in the reference): the modes of the run come from a field instead of ZD_Seed
+// (zd_generate_field); read with zd_param_file_string.  The file is a raw little-endian array [z][y][x]: 4 PPD^3 bytes = float32 (the
+// layout of the density file a ZD_qdensity = 1 run writes), 8 PPD^3 bytes = float64.  It is mapped, not read: the library uploads it in
+// chunks of planes.
+struct FieldKeys {
+    char filename[1024] = "";
+    int32_t kind = ZD_FIELD_DENSITY, dtype = ZD_FIELD_F32;
+    const void *data = nullptr;
+};
+static int read_field_keys(const char *path, FieldKeys &k) {
+    char kind[1024];
+    if (zd_param_file_string(path, "ZD_Field_filename", k.filename, sizeof(k.filename)) || zd_param_file_string(path, "ZD_Field_kind", kind, sizeof(kind)))
+        return 1;
+    if (!k.filename[0]) {
+        if (kind[0]) {
+            fprintf(stderr, "zeldovich_hip: ZD_Field_kind needs ZD_Field_filename (the field it describes)\n");
+            return 1;
+        }
+        return 0;
+    }
+    if (kind[0] && strcmp(kind, "density") && strcmp(kind, "white")) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field_kind = %s must be \"density\" or \"white\"\n", kind);
+        return 1;
+    }
+    k.kind = !strcmp(kind, "white") ? ZD_FIELD_WHITE : ZD_FIELD_DENSITY;
+    return 0;
+}
+// the file against PPD, mapped; non-zero (one line) if it cannot be read or has neither size
+static int map_field(FieldKeys &k, int64_t ppd) {
+    const int fd = open(k.filename, O_RDONLY);
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb)) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field_filename = %s cannot be read\n", k.filename);
+        if (fd >= 0) close(fd);
+        return 1;
+    }
+    const unsigned long long n3 = (unsigned long long) ppd * ppd * ppd, have = (unsigned long long) sb.st_size;
+    if (have != 4 * n3 && have != 8 * n3) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field_filename = %s holds %llu bytes: a field of PPD = %lld is %llu bytes of float32 or %llu bytes of float64\n",
+                k.filename, have, (long long) ppd, 4 * n3, 8 * n3);
+        close(fd);
+        return 1;
+    }
+    k.dtype = have == 8 * n3 ? ZD_FIELD_F64 : ZD_FIELD_F32;
+    void *m = mmap(nullptr, (size_t) have, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (m == MAP_FAILED) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field_filename = %s cannot be mapped\n", k.filename);
+        return 1;
+    }
+    k.data = m;
+    return 0;
+}
+
 int main(int argc, char *argv[]) {
     if (argc != 2) {
         fprintf(stderr, "Usage: %s param_file\n", argv[0]);
@@ -477,6 +532,8 @@ int main(int argc, char *argv[]) {
     if (read_lpt_keys(argv[1], lk)) exit(1);
     GlassKeys gk;
     if (read_glass_keys(argv[1], gk)) exit(1);
+    FieldKeys fk;
+    if (read_field_keys(argv[1], fk)) exit(1);
     zd_params p;
     zd_param_strings s;
     if (zd_params_from_file(argv[1], &p, &s)) {
@@ -493,6 +550,18 @@ int main(int argc, char *argv[]) {
         if (zd_pk_create_powerlaw(s.Pk_powerlaw_index, s.Pk_norm, s.Pk_sigma, s.Pk_sigma_ratio, s.Pk_smooth,
                                   s.qPk_fix_to_mean, p.boxsize, &pkh, &pk))
             return 1;
+    }
+    if (fk.filename[0]) {
+        // (what reads the SEEDED modes of the parameters again — the self-checks, the band-power table — or runs its own passes)
+        const char *other = gk.filename[0] ? "ZD_Glass_filename" : s.SelfCheck > 0 ? "ZD_SelfCheck" : s.Pk_measured_filename[0] ? "ZD_Pk_measured_filename"
+                            : (lk.selfcheck > 0 || lk.pk_filename[0]) ? "ZD_LPT_SelfCheck / ZD_LPT_Pk_filename" : nullptr;
+        if (other) {
+            fprintf(stderr, "zeldovich_hip: ZD_Field_filename does not run together with %s on the command line (the plan calls of the library do)\n", other);
+            exit(1);
+        }
+        if (map_field(fk, p.ppd)) exit(1);
+        fprintf(stderr, "field: %s, %s, PPD %lld\n", fk.kind == ZD_FIELD_WHITE ? "white" : "density", fk.dtype == ZD_FIELD_F64 ? "float64" : "float32",
+                (long long) p.ppd);
     }
     const int narray   = p.qdensity == 2 ? 1 : (p.qPLT ? 4 : 2);  // zeldovich.cpp:871-876
     const double memory = cube(p.ppd / 1024.0) * narray * 16.0;
@@ -555,7 +624,8 @@ int main(int argc, char *argv[]) {
 
     zd_stats st;
     memset(&st, 0, sizeof(st));
-    if (zd_generate(&p, &pk, eig, eig_ppd, Writer::callback, &w, &st)) {
+    if (fk.filename[0] ? zd_generate_field(&p, &pk, eig, eig_ppd, fk.kind, fk.dtype, fk.data, 0, Writer::callback, &w, &st)
+                       : zd_generate(&p, &pk, eig, eig_ppd, Writer::callback, &w, &st)) {
         fprintf(stderr, "zeldovich: generation failed\n");
         exit(1);
     }
