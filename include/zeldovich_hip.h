@@ -463,6 +463,34 @@ int zd_plan_create_field(const zd_params *p, const zd_pk *pk, const double *eig,
 int zd_generate_field(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t kind, int32_t dtype,
                       const void *field, int32_t field_on_device, zd_slab_cb cb, void *user, zd_stats *out);
 
+/* ---- adjoint of a field run: the gradient with respect to the supplied field ------------------------
+ * What a chain over the initial field needs beside the run itself: the vector-Jacobian product abar = J^T (dL/dq, dL/dv, dL/ddens) of a
+ * scalar loss L.  The definition is pinned in csrc/zd_kernels_field_adj.hip.  All arrays are [z][y][x], components in the order of
+ * the records' d / v members (q_z, q_y, q_x), fftn the forward sum (exp(-i)), N = ppd.  The forward map of a field run is linear:
+ *     D(k) = alive(k) A(|k|^2) fftn(a)(k)       A = 1 / N^3 (ZD_FIELD_DENSITY) or sqrt(zd_pk_power(|k|) / N^3) (ZD_FIELD_WHITE)
+ *     q_j  = N^3 ifftn(i s_j D).real            v_j = N^3 ifftn(i f s_j D).real            delivered density = N^3 ifftn(D).real
+ * alive is the zero rule of a field run (above), asked on the half space the path reads (ky > 0; on ky = 0: kz > 0; on ky = kz = 0:
+ * kx > 0) and mirrored; s_j(k) and f(k) are the generator's per-mode coefficients:
+ *     ZA    s_j = k_j fundamental / k^2,            f = (sqrt(1 + 24 f_cluster) - 1) / 4
+ *     PLT   s_j = rescale e_j fundamental / k^2,    f = (sqrt(1 + 24 e_3 f_cluster) - 1) / 4, the eigenmode of a mode of that half space
+ *           from its own lookup; the mirrored half from s(-k) = -s(k), f(-k) = f(k)
+ * The adjoint takes three real cotangents, each optional (NULL = an exact zero): g_q[z][y][x][3], g_v[z][y][x][3], g_dens[z][y][x], all of
+ * one dtype (ZD_FIELD_F32 / _F64), all on the host or (cot_on_device != 0) all on the device, and writes
+ *     H(k) = alive(k) A(|k|^2) [ sum_j conj(i s_j(k)) ( fftn(g_q,j)(k) + f(k) fftn(g_v,j)(k) ) + fftn(g_dens)(k) ]
+ *     abar = N^3 ifftn(H).real                  float64 [z][y][x] into out_field (a device pointer with out_on_device != 0)
+ * so that <q, g_q> + <v, g_v> + <dens, g_dens> = <a, abar> for every field a.  The call is stateless (the Jacobian does not depend on a:
+ * no plan, no PhiK).  These enter exactly as in a field run: ZD_qPLT, ZD_qPLT_rescale, PLT_target_z, z_initial, ZD_f_cluster, ZD_k_cutoff,
+ * ZD_CornerModes, ZD_qonemode, ZD_one_mode, the box, the power spectrum (white only) and the eigenmode table.  These do not:
+ * ZD_Seed, ICFormat, ZD_qdensity, ZD_qoneslab, the stream factor, the store mode — it is the adjoint of the exact float64 map, whatever
+ * format a forward run would round its records to.  No floating-point atomics: two calls return the same bits.
+ * Memory: two half-space arrays of 8 ppd^3 bytes (one when the result lies on the device: its storage serves as the second until the
+ * inverse writes it), the intake's workspace, staging buffers of as many planes for host arrays; a job that does not fit is refused
+ * with the byte figure.  Refused before the GPU is touched, each with one line that starts
+ * "zeldovich_hip: ZD_Field" and names the option: what zd_generate_field refuses, all three cotangents NULL, ZD_qPLT without a table.
+ * stats (may be NULL): seconds_total and bytes_intermediate of the call. */
+int zd_field_vjp(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t kind, int32_t dtype, const void *g_q,
+                 const void *g_v, const void *g_dens, int32_t cot_on_device, double *out_field, int32_t out_on_device, zd_stats *stats);
+
 /* ---- diagnostics ------------------------------------------------------------------------------
  * Which kernel variants this process has launched so far, and how often: one line "count<TAB>line<TAB>launcher" per launch
  * site of the library, the launcher named with its template arguments (transform length, elements per thread, tile shape,

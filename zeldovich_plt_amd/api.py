@@ -92,7 +92,7 @@ EXPORTED_SYMBOLS = [
     "zd_plan_direct_sum", "zd_direct_sum", "zd_make_eigenmodes", "zd_write_eigmodes", "zd_param_file_string",
     "zd_plan_lpt_direct_sum", "zd_lpt_direct_sum", "zd_plan_lpt_power", "zd_lpt_power",
     "zd_interp_create", "zd_interp_add_plane", "zd_interp_result", "zd_interp_destroy", "zd_plan_interp", "zd_displace",
-    "zd_plan_create_field", "zd_generate_field",
+    "zd_plan_create_field", "zd_generate_field", "zd_field_vjp",
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
@@ -219,6 +219,7 @@ def _load(path, testing):
     L.zd_displace.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i64, vp, i64, i64, PARTICLE_CB, vp, C.POINTER(ZdStats)]
     L.zd_plan_create_field.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i32, vp, i32, C.POINTER(vp)]
     L.zd_generate_field.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i32, vp, i32, SLAB_CB, vp, C.POINTER(ZdStats)]
+    L.zd_field_vjp.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i32, vp, vp, vp, i32, vp, i32, C.POINTER(ZdStats)]
     L.zd_dispatch_report.argtypes = [C.c_char_p, i64]
     L.zd_dispatch_report.restype = i64
     return L
@@ -457,6 +458,95 @@ def generate_field(params, ps, field, kind="density", eig=None, collect=True):
         eigp, eig_ppd = eig.ctypes.data, eig.shape[0]
     return _collecting_run(params, collect, lambda cb, st: L.zd_generate_field(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, kcode, dcode,
                                                                                ptr, on_device, cb, None, C.byref(st)), "zd_generate_field")
+
+
+def _cotangent_args(named, ppd):
+    """(dtype code, on_device, [pointer or None, ...], torch device or None) of the cotangents handed to field_vjp: numpy arrays or
+    torch tensors on the GPU, all of one kind and dtype (float32 or float64), C-contiguous, g_q / g_v of shape (ppd, ppd, ppd, 3), g_dens
+    (ppd, ppd, ppd).  Anything else raises before the library is called."""
+    n = int(ppd)
+    given = [(name, a) for name, a in named if a is not None]
+    if not given:
+        raise ValueError("field_vjp: at least one of g_q, g_v, g_dens expected")
+    dtypes, devices, ptrs = set(), set(), []
+    for name, a in named:
+        if a is None:
+            ptrs.append(None)
+            continue
+        shape = (n, n, n) if name == "g_dens" else (n, n, n, 3)
+        if isinstance(a, np.ndarray):
+            if a.dtype not in (np.float32, np.float64):
+                raise TypeError("%s: float32 or float64 expected (got %s)" % (name, a.dtype))
+            if a.shape != shape:
+                raise ValueError("%s: shape %r expected (got %r)" % (name, shape, a.shape))
+            if not a.flags["C_CONTIGUOUS"]:
+                raise ValueError("%s: a C-contiguous array expected" % name)
+            dtypes.add(int(a.dtype == np.float64))
+            devices.add(None)
+            ptrs.append(a.ctypes.data)
+        elif type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr"):
+            import torch
+            if not a.is_cuda:
+                raise ValueError("%s: a torch tensor must live on the GPU (pass a numpy array for host data)" % name)
+            if a.dtype not in (torch.float32, torch.float64):
+                raise TypeError("%s: float32 or float64 expected (got %s)" % (name, a.dtype))
+            if tuple(a.shape) != shape:
+                raise ValueError("%s: shape %r expected (got %r)" % (name, shape, tuple(a.shape)))
+            if not a.is_contiguous():
+                raise ValueError("%s: a C-contiguous tensor expected" % name)
+            dtypes.add(int(a.dtype == torch.float64))
+            devices.add(a.device)
+            ptrs.append(a.data_ptr())
+        else:
+            raise TypeError("%s: a numpy array or a torch tensor on the GPU expected (got %s)" % (name, type(a).__name__))
+    if len(dtypes) != 1:
+        raise TypeError("field_vjp: the cotangents must share one dtype")
+    if len(devices) != 1:
+        raise ValueError("field_vjp: the cotangents must all be numpy arrays or all be tensors on one GPU")
+    device = devices.pop()
+    return dtypes.pop(), int(device is not None), ptrs, device
+
+
+def field_vjp(params, ps, g_q=None, g_v=None, g_dens=None, kind="density", eig=None, out=None):
+    """The adjoint of generate_field's linear map field -> (d, v, density) (zd_field_vjp; definition in csrc/zd_kernels_field_adj.hip):
+    the gradient of a scalar loss with respect to the field, float64 [z][y][x], from its gradients g_q, g_v (ppd, ppd, ppd, 3; components
+    in the order of the records' d / v members) and g_dens (ppd, ppd, ppd).  Each cotangent is optional, None is an exact zero.  numpy
+    arrays give a numpy array, torch tensors on the GPU a tensor there; out= (float64, C-contiguous, of either sort) is filled and
+    returned instead."""
+    if kind not in FIELD_KINDS:
+        raise ValueError("field kind must be one of %s (got %r)" % (sorted(FIELD_KINDS), kind))
+    n = int(params.ppd)
+    dcode, on_device, ptrs, device = _cotangent_args((("g_q", g_q), ("g_v", g_v), ("g_dens", g_dens)), n)
+    if out is None:
+        if on_device:
+            import torch
+            out = torch.empty((n, n, n), dtype=torch.float64, device=device)
+        else:
+            out = np.empty((n, n, n), dtype=np.float64)
+    if isinstance(out, np.ndarray):
+        if out.dtype != np.float64 or out.shape != (n, n, n) or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise ValueError("out: a writeable C-contiguous float64 array of shape (%d, %d, %d) expected" % (n, n, n))
+        outp, out_on_device = out.ctypes.data, 0
+    elif type(out).__module__.split(".")[0] == "torch" and hasattr(out, "data_ptr"):
+        import torch
+        if not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (n, n, n) or not out.is_contiguous():
+            raise ValueError("out: a C-contiguous float64 tensor of shape (%d, %d, %d) on the GPU expected" % (n, n, n))
+        outp, out_on_device = out.data_ptr(), 1
+    else:
+        raise TypeError("out: a numpy array or a torch tensor on the GPU expected (got %s)" % type(out).__name__)
+    if on_device or out_on_device:
+        import torch
+        torch.cuda.synchronize()  # the library works on its own stream
+    L = load_library()
+    eigp, eig_ppd = (None, 0)
+    if eig is not None:
+        eig = np.ascontiguousarray(eig, dtype=np.float64)
+        eigp, eig_ppd = eig.ctypes.data, eig.shape[0]
+    rc = L.zd_field_vjp(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, FIELD_KINDS[kind], dcode, ptrs[0], ptrs[1], ptrs[2], on_device,
+                        outp, out_on_device, None)
+    if rc:
+        raise RuntimeError("zd_field_vjp failed (rc=%d); see stderr" % rc)
+    return out
 
 
 PLT_MAX_PPD = 512  # ZD_PLT_MAX_PPD

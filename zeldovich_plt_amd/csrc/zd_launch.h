@@ -182,6 +182,19 @@ int launch_field_x(int N, const void *src, int is_f32, const void *tw, void *wor
 int launch_field_y(int N, const void *tw, const void *work, int z0, int nplanes, void *phik, hipStream_t st);
 // z lines of phik in place; the store conjugates, applies the zero rule of g and multiplies by amp[kx^2 + ky^2 + kz^2]
 int launch_field_z(const GenConst &g, const void *tw, const double *amp, void *phik, hipStream_t st);
+// ---- adjoint of a field run (zd_kernels_field_adj.hip): cotangents -> H[ky < N/2][kz][x] -> abar[z][y][x] ----
+// rows of the planes [0, nplanes) of the cotangents a, b (b may be NULL; float32 or float64, [plane][y][x][nc]), component comp:
+// fa a + fb b through the x lines into work[plane][y][x]; launch_field_y then takes the columns into T[ky][z][x]
+int launch_field_adj_x(int N, const void *a, const void *b, double fa, double fb, int is_f32, int nc, int comp, const void *tw, void *work,
+                       int nplanes, hipStream_t st);
+// z lines of T; the store conjugates and puts this pass's term into H (first != 0: written, otherwise added): coef 0 = alive A conj(i s_comp),
+// 1 = the same times f (PLT velocities), 2 = alive A (density)
+int launch_field_adj_z(const GenConst &g, const void *tw, const double *amp, const void *T, void *H, int comp, int coef, int first, hipStream_t st);
+// the inverse: z lines of H in place (weight 1 on ky = 0, 2 on the other rows), columns of the planes [z0, z0 + nplanes) into
+// work[plane][y][x], rows of the workspace with the real part into out[plane][y][x]
+int launch_field_adj_iz(int N, const void *tw, void *H, hipStream_t st);
+int launch_field_adj_iy(int N, const void *tw, const void *H, int z0, int nplanes, void *work, hipStream_t st);
+int launch_field_adj_ix(int N, const void *tw, const void *work, double *out, int nplanes, hipStream_t st);
 // ---- ZD_Version = 1 streams (zd_kernels_v1.hip) ----
 int launch_v1_seed(unsigned long long seed, int block, V1Stream *streams, hipStream_t st);
 int launch_v1_draw(const GenConst &g, int block, int ky0, int ky_stride, int nrows, V1Stream *streams, void *dev, int *err,
