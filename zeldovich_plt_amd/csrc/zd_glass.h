@@ -1,4 +1,4 @@
-// zd_glass.h — what zd_kernels_glass.hip (the interpolation object and its kernels) shares with zd_capi.cpp (zd_plan_interp,
+// zd_glass.h — what zd_kernels_glass.hip (the interpolation object and its kernels) shares with zd_capi_interp.cpp (zd_plan_interp,
 // zd_displace): the refusals of a particle load, the object of one sweep of a tiled load, the memory it takes.
 #pragma once
 #include <stddef.h>

@@ -2425,7 +2425,7 @@ __global__ void k_copy16(const uint4 *__restrict__ in, uint4 *__restrict__ out, 
 #endif
 
 // ================================================================================================
-// launchers (C++ linkage inside the library; the C ABI lives in zd_capi.cpp)
+// launchers (C++ linkage inside the library; the C ABI lives in the zd_capi*.cpp units)
 
 
 namespace zd {

@@ -26,7 +26,7 @@
 //   alpha D + f2 gamma S.
 //
 // AS BUILT
-//   Second-order round (zd_capi.cpp make_lpt2_source; once per plan, the whole field resident, stream factor 1): four passes over
+//   Second-order round (zd_capi_rounds.cpp make_lpt2_source; once per plan, the whole field resident, stream factor 1): four passes over
 //   ONE complex array that packs two Hermitian gradient fields as A + iB,
 //        pass 1: (psi_xx, psi_yy + psi_zz)   pass 2: (psi_yy, psi_zz)   pass 3: (psi_xy, psi_xz)   pass 4: (psi_yz, 0),
 //   each one k_gen_lpt2<2> -> k_zfft -> k_yfft (the one-array store of the f_NL phi round) -> k_xlpt2, which transforms an x line

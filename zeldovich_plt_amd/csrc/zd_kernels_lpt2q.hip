@@ -141,7 +141,7 @@ static int launch_lpt2q_zsrc_t(const cplx *tw, int N, const void *store, long lo
 // widths of REFQ_SIZES (zd_kernels_np2_ref.hip): its W neighbouring columns are what coalesces.  An x line is contiguous whatever W is,
 // and at P = 512 eight lines are 768 threads, which caps a thread at 168 registers (404 bytes of scratch per lane); four lines are 384
 // threads with the whole register file and half the LDS, so two workgroups share a CU.  PPD = 2048 (M = 3072) does not fit one GPU
-// (zd_capi.cpp lpt2_round_bytes).
+// (zd_capi_sizing.cpp lpt2_round_bytes).
 #define LPT2Q_SIZES(X) X(16, 3, 16, 16) X(32, 3, 16, 16) X(64, 3, 16, 16) X(128, 3, 16, 16) X(256, 3, 8, 8) X(512, 3, 4, 8)
 
 int launch_lpt2q_xsrc(int m, const void *tw, int pass, void *data, long long pitch, long long nlines, double *acc, hipStream_t st) {

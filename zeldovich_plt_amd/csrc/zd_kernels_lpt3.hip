@@ -23,7 +23,7 @@
 //      terms out (bit 1 = 3a, 2 = 3b, 4 = 3c): a term that is out has coefficient 0.
 //
 // AS BUILT
-//   Third-order round (zd_capi.cpp make_lpt3_sources; once per plan, after the second-order round, S(k) resident, stream factor 1).
+//   Third-order round (zd_capi_rounds.cpp make_lpt3_sources; once per plan, after the second-order round, S(k) resident, stream factor 1).
 //   Six pair passes ab = xx, yy, zz, xy, xz, yz over the ONE complex array of the second-order round's plan: k_gen_lpt3<2> packs
 //   T_ab[D] + i T_ab[S] (the real, even coefficient k_a k_b / k^2 applied to the regenerated D and to S(k) read at the mode) ->
 //   k_zfft -> k_yfft -> k_xlpt3, which transforms an x line in registers and writes Re and Im to two real N^3 arrays.  The twelve

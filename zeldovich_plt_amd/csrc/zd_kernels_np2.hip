@@ -547,7 +547,7 @@ int launch_zfft_fields_np2(int L, const FieldLayout &F, const StoreLayout &S, in
     if (L == 100) return launch_zfft_fq_t<4, 4, 25, 4>(F, S, ky0, kyloc0, nky, Y, (const cplx *) tw, out, st);
     if (L == 60) return launch_zfft_fq_t<4, 4, 15, 4>(F, S, ky0, kyloc0, nky, Y, (const cplx *) tw, out, st);
     // 8 * Q (round 5): eight elements per thread, one thread per sub-line — the half-length lines of the density-only passes that
-    // precede the PLT passes of a PLT + ZD_qdensity = 1 run (zd_capi.cpp plt_dens_split: stream factors R and 2R; PPD = 3456 at R = 8 needs
+    // precede the PLT passes of a PLT + ZD_qdensity = 1 run (zd_route.h plt_dens_split: stream factors R and 2R; PPD = 3456 at R = 8 needs
     // 216 = 8 * 27), and more stream factors to choose from in general
     if (L == 24) return launch_zfft_fq_t<8, 8, 3, 4>(F, S, ky0, kyloc0, nky, Y, (const cplx *) tw, out, st);
     if (L == 40) return launch_zfft_fq_t<8, 8, 5, 4>(F, S, ky0, kyloc0, nky, Y, (const cplx *) tw, out, st);

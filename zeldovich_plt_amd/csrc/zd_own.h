@@ -1,4 +1,4 @@
-// zd_own.h — move-only owners of the HIP resources of the host layer (zd_capi.cpp, zd_multi.cpp, the host launchers of
+// zd_own.h — move-only owners of the HIP resources of the host layer (zd_capi*.cpp, zd_multi.cpp, the host launchers of
 // zd_kernels_pk.hip / zd_kernels_ds.hip): device and pinned buffers, events, streams, plans.  A handle converts to the raw
 // pointer / handle it owns, so launch call sites read as before; the structs passed to kernels keep raw pointers (.get()).
 #pragma once
@@ -12,7 +12,7 @@
 
 struct zd_plan;
 extern "C" void zd_plan_destroy(zd_plan *pl);
-hipError_t zd_store_alloc(void **p, size_t bytes);  // zd_capi.cpp: hipMalloc, NaN-filled under zd_test_poison
+hipError_t zd_store_alloc(void **p, size_t bytes);  // zd_capi_diag.cpp: hipMalloc, NaN-filled under zd_test_poison
 
 namespace zdown {
 

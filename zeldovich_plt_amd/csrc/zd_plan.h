@@ -1,4 +1,4 @@
-// zd_plan.h — the plan object behind the staged C ABI (include/zeldovich_hip.h), shared by zd_capi.cpp (single-rank
+// zd_plan.h — the plan object behind the staged C ABI (include/zeldovich_hip.h), shared by the zd_capi*.cpp units (single-rank
 // stages) and zd_multi.cpp (the in-library multi-GPU driver).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,6 +20,8 @@ struct zd_plan {
     zd_params p;
     int rank = 0, nranks = 1;
     int N = 0, half = 0, narray = 0, R = 1, L = 0, Hq = 0, Zq = 0;
+    int family = 0;            // the kernel family of the route this plan was built from (zd_route.h FAM_*): the stages pick their kernels by it
+    bool twr = false;          // reference arrays (family FAM_REF_COMPOSITE): the lines use the composite twiddles d_twr_*, else the Bluestein tables
     int pack = zd::PACK_NONE;  // what the store holds (zd_device.h PACK_*)
     int npass = 1, pstep = 1;  // passes per run; planes a store plane delivers (2 with PACK_ZAPAIR)
     bool var_pending = true;   // packed stores: the next Z stage accumulates sum |D|^2
@@ -90,7 +92,7 @@ struct zd_plan {
     bool field = false;  // PhiK is a caller-supplied field (zd_plan_create_field): D = PhiK itself, d_fnlM a table of ones
     zdown::DevBuf<zdfft::cplx> d_lpt3_owned[4];  // ZD_q3LPT: P3(k), C_x(k), C_y(k), C_z(k) of the third-order round, handed over likewise
     // any even PPD (zd_kernels_any.hip): Bluestein tables for the lengths L (z lines) and N (y, x lines)
-    bool any = false;
+    bool any = false;  // family >= FAM_REF_COMPOSITE: the reference's arrays as a [plane][array][y][x] store
     zd::AnyTab tabL = {}, tabN = {};
     zd::AnyLayout AL = {};
     zdown::DevBuf<zdfft::cplx> d_any[6];
@@ -108,7 +110,7 @@ struct zd_plan {
     int64_t bytes_sent = 0;  // N > 1 ranks: accounted by zd_plan_run_pass, reported and reset by zd_plan_stats
 };
 
-// internal entry points shared by zd_capi.cpp and zd_multi.cpp
+// internal entry points shared by the zd_capi*.cpp units and zd_multi.cpp
 extern "C" {
 int zd_plan_stage_y_group(zd_plan *pl, void *d_recv, int chunk_planes, int nplanes, void *hip_stream);
 int zd_plan_stage_x_group(zd_plan *pl, int residue, const void *d_recv, int chunk_planes, int64_t plane0, int64_t gplane0,

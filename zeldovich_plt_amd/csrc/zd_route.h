@@ -15,7 +15,7 @@
 // Tuning / ablation knobs (environment variables ZD_ABLATE, ZD_PRUNE, ZD_NT, ZD_LAYOUT, ...) exist only in the
 // -DZD_TUNING build (make tuning -> build/libzeldovich_hip_tuning.so, used by scripts/ through ZD_LIB_PATH).
 // The product library never reads the environment: the names do not even reach its binary.  (Global, macro in the product: this
-// header is for zd_capi.cpp, and for zd_kernels_lpt_ds.hip, which asks the LPT refusals and coefficients.)
+// header is for the zd_capi*.cpp units, and for zd_kernels_lpt_ds.hip, which asks the LPT refusals and coefficients.)
 #ifdef ZD_TUNING
 static inline const char *tune_env(const char *name) { return getenv(name); }
 #else
@@ -87,6 +87,16 @@ inline bool plt_dens_split(const zd_params *p, int nranks) {
     return p->qPLT && p->qdensity == 1 && nranks == 1 && composite_options(p) && !tune_env("ZD_NO_DENS_SPLIT");
 }
 
+// The largest wavenumber per axis that the zero rule keeps (zeldovich.cpp:350-353), and whether the rule leaves every mode with a
+// component on the Nyquist plane |k_i| = N/2 at zero: the |k_i| == kmax rule does it when kmax == N/2 (k_cutoff = 1), the spherical cut
+// when k_cutoff >= 1 and CornerModes is off.  Otherwise (e.g. CornerModes with k_cutoff = 2) the reference keeps independent,
+// non-Hermitian draws there and takes Re/Im of the mixed field (zeldovich.cpp:350-356).
+inline int kmax(int half, double k_cutoff) { return (int) ((double) half * (1.0 / k_cutoff) + .5); }
+inline bool nyquist_dead(const zd_params *p) {
+    const int half = (int) (p->ppd / 2);
+    return kmax(half, p->k_cutoff) == half || (!p->corner_modes && p->k_cutoff >= 1.0);
+}
+
 // Second-order displacements (zd_params.q2LPT; definition in zd_kernels_lpt2.hip).  The second-order round keeps the whole field
 // resident on one GPU, on the power-of-two engine, with the counter streams of ZD_Version 2; the final pass fills the reference's
 // four arrays (the PLT shape: velocities are a field of their own), which carry no eigenmodes, no f_NL and no density output here.
@@ -100,11 +110,7 @@ inline const char *lpt2_refusal(const zd_params *p, int nranks) {
     if (p->version == 1) return "ZD_q2LPT = 1 needs the counter streams of ZD_Version = 2";
     if (nranks != 1 || p->ngpu > 1) return "ZD_q2LPT = 1 runs on one GPU (one rank)";
     if (!is_pow2(p->ppd) || p->ppd < 32 || p->ppd > 2048) return "ZD_q2LPT = 1 needs PPD a power of two in [32, 2048]";
-    {   // the nyquist_dead condition of pack_mode
-        const int half = (int) (p->ppd / 2), kmax = (int) ((double) half * (1.0 / p->k_cutoff) + .5);
-        if (!(kmax == half || (!p->corner_modes && p->k_cutoff >= 1.0)))
-            return "ZD_q2LPT = 1 is not supported with live Nyquist planes (ZD_CornerModes with ZD_k_cutoff != 1)";
-    }
+    if (!nyquist_dead(p)) return "ZD_q2LPT = 1 is not supported with live Nyquist planes (ZD_CornerModes with ZD_k_cutoff != 1)";
     return nullptr;
 }
 // ZD_2LPT_dealias (zd_params.lpt2_dealias; step 2' of the definition, zd_kernels_lpt2.hip): the second-order round on the lattice of
@@ -158,15 +164,9 @@ inline int pack_mode(const zd_params *p, int R) {
     if (p->store_mode == ZD_STORE_REFERENCE || p->q2LPT) return PACK_NONE;  // (second order: the final pass fills the reference's arrays)
     if ((p->qdensity != 0 && !dens_fields(p)) || p->f_NL != 0.) return PACK_NONE;
     if (p->qoneslab >= 0) return PACK_NONE;  // density_variance is then the sum over that one slab (output.cpp:197)
-    {   // The packed stores treat every field as the transform of a REAL field (Hermitian modes) and take
-        // density_variance from sum |D|^2.  That needs every mode with a component on the Nyquist plane |k_i| = N/2 to
-        // be zero: the |k_i| == kmax rule does it when kmax == N/2 (k_cutoff = 1), the spherical cut when k_cutoff >= 1
-        // and CornerModes is off.  Otherwise (e.g. CornerModes with k_cutoff = 2) the reference keeps independent,
-        // non-Hermitian draws there and takes Re/Im of the mixed field (zeldovich.cpp:350-356): reference arrays.
-        const int half = (int) (p->ppd / 2), kmax = (int) ((double) half * (1.0 / p->k_cutoff) + .5);
-        const bool nyquist_dead = kmax == half || (!p->corner_modes && p->k_cutoff >= 1.0);
-        if (!nyquist_dead) return PACK_NONE;
-    }
+    // The packed stores treat every field as the transform of a REAL field (Hermitian modes) and take density_variance from
+    // sum |D|^2.  That needs every mode with a component on the Nyquist plane to be zero (nyquist_dead): reference arrays otherwise.
+    if (!nyquist_dead(p)) return PACK_NONE;
     // PLT: the three packed arrays by default; its field store (six half-space sums) only on request — measured slower
     // (PPD=2048 PLT+rescale 0.553 -> 0.609 s: every array of the y stage needs two potentials, each fetched twice, and the
     // 148-VGPR PLT generator leaves no room for the z FFT beside it anyway)
@@ -320,7 +320,7 @@ inline bool split_routes(const zd_params *p, int R, zd_params *pa, zd_params *pb
 // for launch_xfft_t, _seq_t, _seq_plt_t, _two_t, _q2_plt_t), the key as it appears among their template arguments, and the answer of
 // the table's predicate (zd_tables.h).  route_stages restates the selection code of the stages — launch_zstage_fft, fused_stage_z,
 // any_stage_z, zd_plan_stage_y_group, zd_plan_stage_x_group, make_phik / zd_plan_phi_xy_group / zd_plan_phi_zfwd, make_lpt2_source,
-// make_lpt3_sources (zd_capi.cpp) — for the plan that plan_create_one builds from a Route; tests/test_gpu_route_edges.py holds it to what
+// make_lpt3_sources (zd_capi_stages.cpp, zd_capi_rounds.cpp) — for the plan that plan_create_one builds from a Route; tests/test_gpu_route_edges.py holds it to what
 // a run really launches.  Not listed: the generators (launch_gen takes every z line that is a multiple of 4, which every accepted
 // family's are, and any length on the reference's arrays) and kernels without a size table (scatter, emit, pointwise).
 struct StageKey {
@@ -348,6 +348,16 @@ struct StageList {
         return nullptr;
     }
 };
+
+// Fused Z stage of the packed PLT store (zd_kernels_fz.hip: generator + z FFT in one kernel), as far as parameters and route decide it:
+// the packed store by the store mode's own choice, one rank with the rows of a plane in one block, z lines the kernel has, version-2
+// streams, the whole field, the main pass, and a dead kz = N/2 plane that the cut — not the corner rule alone — leaves dead (the
+// kernel never draws it).  plan_block_layout adds what only the plan knows (the table generator, every prune bit).  `pack` is
+// PACK_PLT3 only on a main-role plan without ZD_q2LPT, so the other roles and a PhiK never get past the first term.
+inline bool fused_z_route(const zd_params *p, int pack, int N, int L, int role, bool one_block) {
+    return pack == PACK_PLT3 && p->store_mode == ZD_STORE_AUTO && one_block && genz_plt_supported(N, L) && p->version != 1
+           && p->qoneslab < 0 && role == ROLE_MAIN && p->k_cutoff >= 1.0 && nyquist_dead(p) && !tune_env("ZD_NO_FUSED_Z");
+}
 
 // the stages of ONE plan of shape rt (no sub-rounds)
 inline void plan_stages(const Route &rt, const zd_params *p, int role, int nranks, const char *prefix, StageList &out) {
@@ -411,11 +421,7 @@ inline void plan_stages(const Route &rt, const zd_params *p, int role, int nrank
     out.add(prefix, "z", "launch_zfft_t", has_zfft(L), "L = %d,", L);
     {   // the fused generator + z FFT of the packed PLT store (plan_block_layout) where the power table allows it (at most 512 spline
         // segments): plane-interleaved rows, 4 planes; the two-kernel stage on plain rows otherwise — a job needs both
-        const int half = N / 2, kmax = (int) ((double) half * (1.0 / p->k_cutoff) + .5);
-        const bool fused = rt.pack == PACK_PLT3 && p->store_mode == ZD_STORE_AUTO && one_block && genz_plt_supported(N, L) && p->version != 1
-                           && p->qoneslab < 0 && role == ROLE_MAIN && p->k_cutoff >= 1.0 && (kmax == half || !p->corner_modes)
-                           && !tune_env("ZD_NO_FUSED_Z");
-        if (fused) {
+        if (fused_z_route(p, rt.pack, N, L, role, one_block != 0)) {
             out.add(prefix, "z fused", "launch_genz_t", genz_plt_supported(N, L), "L = %d, R = %d,", L, rt.R);
             out.add(prefix, "y fused", "launch_yfft_t", has_yfft(N, 2, one_block, rt.Zq), "N = %d,", N);
             out.add(prefix, "x fused", "launch_xfft", has_xfft(N, rt.narray, rt.pack, 2, one_block), "N = %d,", N);
