@@ -463,6 +463,30 @@ int zd_plan_create_field(const zd_params *p, const zd_pk *pk, const double *eig,
 int zd_generate_field(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int32_t kind, int32_t dtype,
                       const void *field, int32_t field_on_device, zd_slab_cb cb, void *user, zd_stats *out);
 
+/* ---- second order (2LPT) on a caller-supplied field: the order is an argument of the field call ------
+ * Definition (pinned in csrc/zd_kernels_lpt2_field.hip).  Start from D(k), the modes of the supplied field exactly as a first-order field
+ * run holds them (the intake above: zero rule, 1 / ppd^3 or the white-noise amplitude, the |k_i| = ppd/2 planes cleared), and apply steps
+ * 1 - 5 of the DEFINITION in csrc/zd_kernels_lpt2.hip unchanged: gradients -k_a k_b D / k^2, S(x) on the ppd^3 lattice without
+ * de-aliasing, S(k) = ppd^-3 x the forward sum times the alive mask with S(0) = 0, positions from D + gamma S, velocities from
+ * alpha D + f2 gamma S; gamma = -lpt2_ratio, alpha and f2 resolved from lpt2_ratio, lpt2_f2 and f_cluster of the parameters as for
+ * ZD_q2LPT.  It is the seeded ZD_q2LPT run with "D drawn from its counter" replaced by "D read from the field".  ZD_Seed is ignored.
+ *   order   1: exactly zd_generate_field / zd_plan_create_field without an eigenmode table;  2: the above;  anything else is refused
+ *           (3: third order on a field is not built).
+ * The parameters come with q2LPT = q3LPT = lpt2_dealias = 0 (otherwise the refusal of a field run, in its words); inside, an order-2 job
+ * runs as the q2LPT job it is, on the reference's four arrays at any stream factor, and the plan's parameters read back q2LPT = 1.
+ * Accepted with order = 2: ppd a power of two in [32, 1024] (2048: the second-order round alone would hold ~275 GB), one GPU, ZA, every
+ * ICFormat, ZD_k_cutoff, ZD_qonemode, ZD_f_cluster, ZD_qoneslab.  Refused with one line that starts "zeldovich_hip: ZD_Field" and names
+ * the option: everything a field run refuses, and everything ZD_q2LPT refuses (ZD_qPLT, ZD_f_NL, a density output, ZD_Version = 1, live
+ * Nyquist planes, several GPUs).  Memory: D(k) (8 ppd^3 bytes) stays resident through the round, whose peak is therefore ~32 ppd^3
+ * bytes; afterwards D(k) and S(k) (16 ppd^3 bytes) sit beside the store of a pass; both belong to the plan.  A job that does not fit
+ * is refused with the byte figure.  zd_plan_lpt_direct_sum and zd_plan_lpt_power work on such a plan (order 1 read from D, order 2 from
+ * S); zd_plan_direct_sum and zd_plan_measure_power refuse it as they refuse every second-order plan; the stage calls,
+ * zd_plan_run_passes, zd_plan_stats and zd_plan_interp work as on any plan.  zd_field_vjp is the adjoint of order 1 only. */
+int zd_plan_create_field_lpt(const zd_params *p, const zd_pk *pk, int32_t kind, int32_t dtype, const void *field, int32_t field_on_device,
+                             int32_t order, zd_plan **out);
+int zd_generate_field_lpt(const zd_params *p, const zd_pk *pk, int32_t kind, int32_t dtype, const void *field, int32_t field_on_device,
+                          int32_t order, zd_slab_cb cb, void *user, zd_stats *out);
+
 /* ---- adjoint of a field run: the gradient with respect to the supplied field ------------------------
  * What a chain over the initial field needs beside the run itself: the vector-Jacobian product abar = J^T (dL/dq, dL/dv, dL/ddens) of a
  * scalar loss L.  The definition is pinned in csrc/zd_kernels_field_adj.hip.  All arrays are [z][y][x], components in the order of

@@ -92,7 +92,7 @@ EXPORTED_SYMBOLS = [
     "zd_plan_direct_sum", "zd_direct_sum", "zd_make_eigenmodes", "zd_write_eigmodes", "zd_param_file_string",
     "zd_plan_lpt_direct_sum", "zd_lpt_direct_sum", "zd_plan_lpt_power", "zd_lpt_power",
     "zd_interp_create", "zd_interp_add_plane", "zd_interp_result", "zd_interp_destroy", "zd_plan_interp", "zd_displace",
-    "zd_plan_create_field", "zd_generate_field", "zd_field_vjp",
+    "zd_plan_create_field", "zd_generate_field", "zd_field_vjp", "zd_plan_create_field_lpt", "zd_generate_field_lpt",
 ]
 # test scaffolding: exists only in the -DZD_TESTING library (csrc/zd_testing.h, `make testing`), never in the product
 TESTING_SYMBOLS = ["zd_test_draws", "zd_test_modes", "zd_test_modes_table", "zd_test_v1_words", "zd_test_generate_loopback", "zd_test_fail_rank",
@@ -219,6 +219,8 @@ def _load(path, testing):
     L.zd_displace.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i64, vp, i64, i64, PARTICLE_CB, vp, C.POINTER(ZdStats)]
     L.zd_plan_create_field.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i32, vp, i32, C.POINTER(vp)]
     L.zd_generate_field.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i32, vp, i32, SLAB_CB, vp, C.POINTER(ZdStats)]
+    L.zd_plan_create_field_lpt.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), i32, i32, vp, i32, i32, C.POINTER(vp)]
+    L.zd_generate_field_lpt.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), i32, i32, vp, i32, i32, SLAB_CB, vp, C.POINTER(ZdStats)]
     L.zd_field_vjp.argtypes = [C.POINTER(ZdParams), C.POINTER(ZdPk), vp, i64, i32, i32, vp, vp, vp, i32, vp, i32, C.POINTER(ZdStats)]
     L.zd_dispatch_report.argtypes = [C.c_char_p, i64]
     L.zd_dispatch_report.restype = i64
@@ -417,12 +419,16 @@ def _collecting_run(params, collect, call, what):
 FIELD_KINDS = {"density": 0, "white": 1}  # ZD_FIELD_DENSITY, ZD_FIELD_WHITE
 
 
-def _field_arg(field, ppd, kind):
+def _field_arg(field, ppd, kind, order=1):
     """(kind code, dtype code, pointer, on_device) of a field handed to generate_field / Plan.from_field: a numpy array or a torch
-    tensor on the GPU, float32 or float64, of shape (ppd, ppd, ppd), C-contiguous.  Anything else raises before the library is called."""
+    tensor on the GPU, float32 or float64, of shape (ppd, ppd, ppd), C-contiguous.  Anything else raises before the library is called.
+    (order != 1 at a ppd no higher-order field run takes — not a power of two in [32, 1024]: the library refuses the job by its size
+    before it looks at the field, so the shape is its business.)"""
     if kind not in FIELD_KINDS:
         raise ValueError("field kind must be one of %s (got %r)" % (sorted(FIELD_KINDS), kind))
     n = int(ppd)
+    if order != 1 and not (32 <= n <= 1024 and n & (n - 1) == 0):
+        n = int(field.shape[0]) if getattr(field, "ndim", 0) == 3 else n
     if isinstance(field, np.ndarray):
         if field.dtype not in (np.float32, np.float64):
             raise TypeError("field: float32 or float64 expected (got %s)" % field.dtype)
@@ -446,12 +452,40 @@ def _field_arg(field, ppd, kind):
     raise TypeError("field: a numpy array or a torch tensor on the GPU expected (got %s)" % type(field).__name__)
 
 
-def generate_field(params, ps, field, kind="density", eig=None, collect=True):
+def generate_field(params, ps, field, kind="density", eig=None, collect=True, order=1, on_plane=None):
     """generate() with the modes taken from a caller-supplied real field instead of ZD_Seed (zd_generate_field; definition in
     csrc/zd_kernels_field.hip).  field: numpy array or torch tensor on the GPU, float32 or float64, shape (ppd, ppd, ppd) = [z][y][x],
-    C-contiguous.  kind: "density" (the linear density in the run's units) or "white" (unit-variance white noise, coloured by ps)."""
-    kcode, dcode, ptr, on_device = _field_arg(field, params.ppd, kind)
+    C-contiguous.  kind: "density" (the linear density in the run's units) or "white" (unit-variance white noise, coloured by ps).
+    order: 1 the Zel'dovich run; 2 second order (2LPT) on the field (zd_generate_field_lpt; definition in csrc/zd_kernels_lpt2_field.hip):
+    the parameters come WITHOUT q2LPT, lpt2_ratio and lpt2_f2 of them apply, no eigenmode table.
+    on_plane: a per-plane consumer as generate_planes takes it, on_plane(z, records[y, x]); nothing is accumulated then (through
+    zd_generate_field_lpt at either order: no eigenmode table)."""
+    kcode, dcode, ptr, on_device = _field_arg(field, params.ppd, kind, order)
     L = load_library()
+    if order != 1 or on_plane is not None:
+        if eig is not None:
+            raise ValueError("generate_field: order = %r%s takes no eigenmode table" % (order, "" if on_plane is None else " with on_plane"))
+
+        def call(cb, st):
+            return L.zd_generate_field_lpt(C.byref(params), C.byref(ps.pk), kcode, dcode, ptr, on_device, int(order), cb, None, C.byref(st))
+
+        if on_plane is None:
+            return _collecting_run(params, collect, call, "zd_generate_field_lpt")
+        n, dt, st, count = int(params.ppd), RECORD_DTYPES[_fmt_name(params.icformat)], ZdStats(), [0]
+
+        def _cb(user, z, nrec, recp, densp):
+            count[0] += 1
+            if recp:
+                buf = (C.c_char * (nrec * dt.itemsize)).from_address(recp)
+                return int(on_plane(int(z), np.frombuffer(buf, dtype=dt).reshape(n, n)) or 0)
+            return 0
+
+        rc = call(SLAB_CB(_cb), st)
+        if rc:
+            raise RuntimeError("zd_generate_field_lpt failed (rc=%d); see stderr" % rc)
+        out = _stats_dict(st)
+        out["planes"] = count[0]
+        return out
     eigp, eig_ppd = (None, 0)
     if eig is not None:
         eig = np.ascontiguousarray(eig, dtype=np.float64)
@@ -807,13 +841,18 @@ def generate_planes(params, ps, on_plane, eig=None):
 class Plan:
     """Staged API: one rank's share of the Z and XY stages on device pointers (see the header)."""
 
-    def __init__(self, params, ps, eig=None, rank=0, nranks=1, testing=False, _field=None):
+    def __init__(self, params, ps, eig=None, rank=0, nranks=1, testing=False, _field=None, _order=1):
         self.L = load_testing_library() if testing else load_library()  # testing: the -DZD_TESTING build (zd_test_poison), tests only
         self.params = params
         self._eig = None if eig is None else np.ascontiguousarray(eig, dtype=np.float64)
         h = C.c_void_p()
         eigp, eig_ppd = (None, 0) if self._eig is None else (self._eig.ctypes.data, self._eig.shape[0])
-        if _field is not None:  # from_field: (kind code, dtype code, pointer, on_device)
+        if _field is not None and _order != 1:  # from_field(order=2): a higher order on the field; the plan's parameters read q2LPT = 1
+            if self._eig is not None:
+                raise ValueError("Plan.from_field: order = %r takes no eigenmode table (ZD_qPLT has no second order)" % (_order,))
+            if self.L.zd_plan_create_field_lpt(C.byref(params), C.byref(ps.pk), *_field, int(_order), C.byref(h)):
+                raise RuntimeError("zd_plan_create_field_lpt failed; see stderr")
+        elif _field is not None:  # from_field: (kind code, dtype code, pointer, on_device)
             if self.L.zd_plan_create_field(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, *_field, C.byref(h)):
                 raise RuntimeError("zd_plan_create_field failed; see stderr")
         elif self.L.zd_plan_create(C.byref(params), C.byref(ps.pk), eigp, eig_ppd, rank, nranks, C.byref(h)):
@@ -830,10 +869,11 @@ class Plan:
         self.local_planes = self.L.zd_plan_local_planes(h)
 
     @classmethod
-    def from_field(cls, params, ps, field, kind="density", eig=None):
+    def from_field(cls, params, ps, field, kind="density", eig=None, order=1):
         """a one-rank plan whose modes come from a caller-supplied real field (zd_plan_create_field; see generate_field): every
-        method of a plan works on it.  The field is consumed here: the plan keeps its modes, not the array."""
-        return cls(params, ps, eig=eig, _field=_field_arg(field, params.ppd, kind))
+        method of a plan works on it.  The field is consumed here: the plan keeps its modes, not the array.  order=2: the second-order
+        plan on the field (zd_plan_create_field_lpt): lpt_direct_sum and lpt_power work on it, direct_sum and measure_power refuse it."""
+        return cls(params, ps, eig=eig, _field=_field_arg(field, params.ppd, kind, order), _order=order)
 
     def plane_z(self, residue, local_plane):
         return self.L.zd_plan_plane_z(self.h, residue, local_plane)

@@ -383,7 +383,9 @@ static void plan_zstage_jobs(zd_plan *pl) {
 static int plan_block_layout(zd_plan *pl, int role) {
     const zd_params *p = &pl->p;
     zd::GenConst &g = pl->g;
-    const bool main = !g.gen_phi && !g.phik && !(g.lpt2 >= 1 && g.lpt2 <= 4);  // (the second-order round's x lines read every column too)
+    // (a second-order plan on a caller-supplied field reads D from PhiK where the seeded one draws it: same zero rule, same pruning)
+    const bool every_mode = g.phik && !g.lpt2;
+    const bool main = !g.gen_phi && !every_mode && !(g.lpt2 >= 1 && g.lpt2 <= 4);  // (the second-order round's x lines read every column too)
     zd::StoreLayout &S = pl->S;
     S.N      = pl->N;
     S.half   = pl->half;
@@ -396,7 +398,7 @@ static int plan_block_layout(zd_plan *pl, int role) {
     S.narray = pl->narray;
     S.prune     = tune_env("ZD_PRUNE") ? atoi(tune_env("ZD_PRUNE")) : 7;  // bit 0 k_gen, 1 k_zfft, 2 k_yfft
     S.nt = tune_env("ZD_NT") ? atoi(tune_env("ZD_NT")) : 0;
-    if (g.phik) S.prune = 0;  // f_NL second pass: every mode carries power (the zero rule is bypassed)
+    if (every_mode) S.prune = 0;  // f_NL second pass: every mode carries power (the zero rule is bypassed)
     if (pl->any) S.prune = 0;  // the convolution kernels transform every column: the generator must write every one
     S.kmax      = g.kmax;
     S.fund2     = g.fundamental2;
@@ -714,7 +716,7 @@ void gen_growth(zd::GenConst &g, const zd_params *p) {
 
 // a plan of the shape an accepted route gives; each part above fills its own members; a plan that fails half-way releases what it has
 static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks,
-                           int role, const cplx *phik, bool field, PlanPtr &out) {
+                           int role, const cplx *phik, bool field, const cplx *field_d, PlanPtr &out) {
     PlanPtr plan(new zd_plan);
     zd_plan *pl   = plan.get();
     pl->p         = *p;
@@ -750,7 +752,7 @@ static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk,
     gen_growth(g, p);
     g.eig_ppd = eig_ppd;
     g.gen_phi = role == zd::ROLE_PHI;
-    g.phik    = p->q2LPT ? nullptr : phik;
+    g.phik    = p->q2LPT ? field_d : phik;  // (ZD_q2LPT: phik is S(k), below; PhiK is there only as the modes of a caller-supplied field)
     if (role == zd::ROLE_LPT2_GRAD) g.lpt2 = 1;  // (make_lpt2_source sets the pass in front of every Z stage)
     if (role == zd::ROLE_MAIN && p->q2LPT) {     // final pass: positions from D + gamma S, velocities from alpha D + f2 gamma S
         g.lpt2       = 5;
@@ -772,8 +774,12 @@ static int plan_create_one(const zd_params *p, const Route &rt, const zd_pk *pk,
 }
 
 int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks, int phi_mode,
-                   const cplx *phik, PlanPtr &out, bool field) {
+                   const cplx *phik, PlanPtr &out, bool field, const cplx *field_d) {
     const zd_params pc = zd::canonical(p_in);
+    if (field_d && (!pc.q2LPT || !field || nranks != 1)) {  // (the first order of a field run takes its modes as phik)
+        fprintf(stderr, "zeldovich_hip: ZD_Field: the modes of a field beside S(k) belong to a second-order plan on one rank\n");
+        return 1;
+    }
     const int role = phi_mode == 1 ? zd::ROLE_PHI : phi_mode == 2 ? zd::ROLE_LPT2_GRAD : (phik && !pc.q2LPT) ? zd::ROLE_PHIK : zd::ROLE_MAIN;
     if (pc.q2LPT && role == zd::ROLE_MAIN && !phik) {  // (zd_plan_create and zd_generate run the second-order round first)
         fprintf(stderr, "zeldovich_hip: a ZD_q2LPT plan needs the second-order source\n");
@@ -785,8 +791,8 @@ int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *eig, in
     if (role == zd::ROLE_MAIN && zd::plt_dens_split(&pc, nranks) && have_eig && split_routes(&pc, pc.stream_factor, &pa, &pb, &ra, &rb) && ra.ok()
         && rb.ok()) {
         PlanPtr A, B;
-        if (plan_create_one(&pa, ra, pk, eig, eig_ppd, rank, nranks, role, nullptr, false, A) == 0
-            && plan_create_one(&pb, rb, pk, nullptr, 0, rank, nranks, role, nullptr, false, B) == 0
+        if (plan_create_one(&pa, ra, pk, eig, eig_ppd, rank, nranks, role, nullptr, false, nullptr, A) == 0
+            && plan_create_one(&pb, rb, pk, nullptr, 0, rank, nranks, role, nullptr, false, nullptr, B) == 0
             && A->d_dens_pass.store_alloc((size_t) A->Zq * pc.ppd * pc.ppd) == hipSuccess) {
             A->p            = pc;  // (what the callers read back: ZD_qdensity = 1)
             A->store_bytes_ = std::max(A->store_bytes_, B->store_bytes_);
@@ -801,7 +807,7 @@ int plan_create_ex(const zd_params *p_in, const zd_pk *pk, const double *eig, in
         fprintf(stderr, "zeldovich_hip: %s\n", rt.why);
         return 1;
     }
-    return plan_create_one(&pc, rt, pk, eig, eig_ppd, rank, nranks, role, phik, field, out);
+    return plan_create_one(&pc, rt, pk, eig, eig_ppd, rank, nranks, role, phik, field, field_d, out);
 }
 
 zd_plan::~zd_plan() {  // the members release themselves afterwards

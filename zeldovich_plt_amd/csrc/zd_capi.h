@@ -55,6 +55,8 @@ int64_t fnl_phik_bytes(int64_t N);
 // ZD_q2LPT memory: the source S(k) (half-space rows, PhiK's layout), and the peak of the second-order round before it
 int64_t lpt2_sk_bytes(int64_t N);
 int64_t lpt2_round_bytes(const zd_params *p);
+// second order on a caller-supplied field: the round's peak with D(k) resident beside it
+int64_t field_lpt2_round_bytes(const zd_params *p);
 // ZD_q3LPT memory: the peak of the third-order round
 int64_t lpt3_round_bytes(int64_t N);
 
@@ -71,8 +73,10 @@ void gen_zero_rule(zd::GenConst &g, const zd_params *p);
 void gen_growth(zd::GenConst &g, const zd_params *p);
 // phi_mode 1: first f_NL pass (one array holding phi = D/M); phik != NULL: second pass (D = phik * M).  ZD_q2LPT: phi_mode 2 = the
 // plan of the second-order round's gradient passes; phik != NULL with phi_mode 0 = the final pass, phik holding the source S(k)
+// field_d != NULL (ZD_q2LPT only): the modes D(k) of a caller-supplied field, PhiK's layout; the plan reads them (GenConst::phik with a
+// table of ones) where it would draw, in the gradient passes and in the final pass, beside S(k)
 int plan_create_ex(const zd_params *p, const zd_pk *pk, const double *eig, int64_t eig_ppd, int rank, int nranks, int phi_mode,
-                   const cplx *phik, PlanPtr &out, bool field = false);
+                   const cplx *phik, PlanPtr &out, bool field = false, const cplx *field_d = nullptr);
 // a plan that was made goes to a caller of the C ABI; *out is left alone otherwise
 int hand_over(int rc, PlanPtr &pl, zd_plan **out);
 
@@ -92,8 +96,9 @@ zd::AnyChunks any_chunks(const zd_plan *pl, int chunk_planes);
 int make_phik(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d_phik);
 // the round's peak against the free memory, asked before anything is built (the figure is the message)
 int lpt2_round_fits(const zd_params *p, int64_t free_bytes);
-// ZD_q2LPT: the second-order round (zd_kernels_lpt2.hip), run once; d_sk = S(k)[ky][kz][x], scaled by N^-3 (handed to the caller)
-int make_lpt2_source(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d_sk);
+// ZD_q2LPT: the second-order round (zd_kernels_lpt2.hip), run once; d_sk = S(k)[ky][kz][x], scaled by N^-3 (handed to the caller).
+// field_d != NULL: the gradient passes read D(k) of a caller-supplied field there (zd_kernels_lpt2_field.hip) instead of drawing it
+int make_lpt2_source(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d_sk, const cplx *field_d = nullptr);
 // ZD_q3LPT: the third-order round (zd_kernels_lpt3.hip), run once after the second; d_out[0 .. 3] = P3(k), C_x(k), C_y(k), C_z(k)
 int make_lpt3_sources(const zd_params *p, const zd_pk *pk, const cplx *d_sk, DevBuf<cplx> (&d_out)[4]);
 // a plan of the final pass takes the four spectra over and points its generator at them
@@ -106,10 +111,13 @@ struct FieldSpec {
     int32_t kind, dtype;  // ZD_FIELD_DENSITY / _WHITE, ZD_FIELD_F32 / _F64
     const void *field;    // a[z][y][x], C-contiguous
     int32_t on_device;
+    int32_t order = 1;  // 2: second order on the field (zd_generate_field_lpt, zd_plan_create_field_lpt)
 };
 // The field -> d_phik = D(k)[ky][kz][x] for the half-space rows, zero rule and amplitude applied (owned by the caller, untouched on
 // failure)
 int make_field_phik(const zd_params *p, const zd_pk *pk, const FieldSpec &f, DevBuf<cplx> &d_phik);
+// order 2: the second-order round with D(k) resident beside it against the free memory (the figure is the message)
+int field_lpt2_fits(const zd_params *p, int64_t free_bytes);
 
 // ---- zd_capi_generate.cpp ----
 // zd_generate, and zd_generate_field (fs != NULL: the modes come from the caller's field; its refusals have been asked)

@@ -1,5 +1,5 @@
-// zd_capi_field.cpp — a caller-supplied density or white-noise field: its intake (zd_generate_field, zd_plan_create_field) and the
-// adjoint of a field run (zd_field_vjp).
+// zd_capi_field.cpp — a caller-supplied density or white-noise field: its intake (zd_generate_field, zd_plan_create_field), the second
+// order on it (zd_generate_field_lpt, zd_plan_create_field_lpt) and the adjoint of a first-order field run (zd_field_vjp).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -27,6 +27,46 @@ static int field_refused(const zd_params *p, const zd_pk *pk, const FieldSpec &f
     if (!why[0]) return 0;
     fprintf(stderr, "zeldovich_hip: ZD_Field %s\n", why);
     return 1;
+}
+// ... and what the order argument of zd_generate_field_lpt / zd_plan_create_field_lpt adds (definition: zd_kernels_lpt2_field.hip): the
+// parameters come as a first-order field run's (ZD_q2LPT in them keeps its refusal above); with order = 2 whatever ZD_q2LPT refuses
+// (zd_route.h lpt2_refusal) is refused here, in a field run's words.  The size comes before the field is looked at.
+static int field_order_refused(const zd_params *p, const zd_pk *pk, const FieldSpec &f) {
+    char why[256] = "";
+    const int64_t N = p->ppd;
+    if (f.order == 3) snprintf(why, sizeof why, "order = 3: third order (ZD_q3LPT) on a field is not built");
+    else if (f.order != 1 && f.order != 2) snprintf(why, sizeof why, "order = %d (1: Zel'dovich, 2: second order expected)", f.order);
+    else if (f.order == 2 && !(p->q2LPT || p->q3LPT || p->lpt2_dealias) && is_pow2(N) && N > 1024 && N <= 2048) {
+        zd_params pq = *p;
+        pq.q2LPT     = 1;
+        snprintf(why, sizeof why, "order = 2 needs PPD a power of two in [32, 1024], got PPD = %lld: the second-order round alone would hold %.0f GB",
+                 (long long) N, field_lpt2_round_bytes(&pq) / 1e9);
+    }
+    if (why[0]) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field %s\n", why);
+        return 1;
+    }
+    if (field_refused(p, pk, f)) return 1;
+    if (f.order == 1) return 0;
+    if (p->qPLT) snprintf(why, sizeof why, "order = 2 is not supported together with ZD_qPLT (the second order rides on the ZA fields)");
+    else if (p->qdensity != 0) snprintf(why, sizeof why, "order = 2 is not supported together with a density output (ZD_qdensity = %d)", p->qdensity);
+    else if (!zd::nyquist_dead(p))
+        snprintf(why, sizeof why, "order = 2 is not supported with live Nyquist planes (ZD_CornerModes with ZD_k_cutoff != 1): the source would not be real");
+    else {  // (anything lpt2_refusal learns to refuse later)
+        zd_params pq = *p;
+        pq.q2LPT     = 1;
+        if (const char *r = zd::lpt2_refusal(&pq, 1)) snprintf(why, sizeof why, "order = 2: %s", r);
+    }
+    if (!why[0]) return 0;
+    fprintf(stderr, "zeldovich_hip: ZD_Field %s\n", why);
+    return 1;
+}
+// the second-order round with D(k) resident beside it against the free memory, asked before anything is built (the figure is the message)
+int field_lpt2_fits(const zd_params *p, int64_t free_bytes) {
+    if (field_lpt2_round_bytes(p) <= free_bytes) return 1;
+    fprintf(stderr, "zeldovich_hip: ZD_Field order = 2 needs %.1f GB of HBM at PPD %lld (the second-order round %.1f GB, the modes of the field %.1f GB beside it), %.1f GB are free\n",
+            field_lpt2_round_bytes(p) / 1e9, (long long) p->ppd, lpt2_round_bytes(p) / 1e9, fnl_phik_bytes(p->ppd) / 1e9, free_bytes / 1e9);
+    return 0;
 }
 // planes of the intake's workspace (complex x-stage output) and of the staging buffer of a host field: at least 4, at most 256 MB
 static int field_ws_planes(int64_t N) { return (int) std::min<int64_t>(N, std::max<int64_t>(4, ((int64_t) 1 << 28) / (N * N * 16))); }
@@ -106,6 +146,44 @@ int zd_plan_create_field(const zd_params *p, const zd_pk *pk, const double *eig,
     if (plan_create_ex(p, pk, eig, eig_ppd, 0, 1, 0, d_phik, pl, true)) return 1;
     pl->d_phik_owned = std::move(d_phik);
     *out             = pl.release();
+    return 0;
+}
+
+// ---- second order on the field: order 1 is the call above without an eigenmode table; order 2 runs the q2LPT job with D(k) read from
+// the field (zd_kernels_lpt2_field.hip).  The plan owns D(k) (d_phik_owned, GenConst::phik) and S(k) (d_lpt2_sk_owned, GenConst::lpt2_sk)
+int zd_generate_field_lpt(const zd_params *p, const zd_pk *pk, int32_t kind, int32_t dtype, const void *field, int32_t field_on_device,
+                          int32_t order, zd_slab_cb cb, void *user, zd_stats *out) {
+    if (!p || !pk || !out) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field: zd_generate_field_lpt needs parameters, a power spectrum and a zd_stats\n");
+        return 1;
+    }
+    const FieldSpec fs{kind, dtype, field, field_on_device, order};
+    if (field_order_refused(p, pk, fs)) return 1;
+    zd_params pq = *p;
+    pq.q2LPT     = order == 2;
+    return generate_impl(&pq, pk, nullptr, 0, cb, user, out, &fs);
+}
+int zd_plan_create_field_lpt(const zd_params *p, const zd_pk *pk, int32_t kind, int32_t dtype, const void *field, int32_t field_on_device,
+                             int32_t order, zd_plan **out) {
+    if (!p || !pk || !out) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field: zd_plan_create_field_lpt needs parameters, a power spectrum and a place for the plan\n");
+        return 1;
+    }
+    const FieldSpec fs{kind, dtype, field, field_on_device, order};
+    if (field_order_refused(p, pk, fs)) return 1;
+    if (order == 1) return zd_plan_create_field(p, pk, nullptr, 0, kind, dtype, field, field_on_device, out);
+    zd_params pq = *p;
+    pq.q2LPT     = 1;
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+    if (lpt2_route_check(&pq, 1, 0) || !field_lpt2_fits(&pq, (int64_t) free_b)) return 1;
+    DevBuf<cplx> d_field, d_sk;
+    if (make_field_phik(&pq, pk, fs, d_field) || make_lpt2_source(&pq, pk, d_sk, d_field)) return 1;
+    PlanPtr pl;
+    if (plan_create_ex(&pq, pk, nullptr, 0, 0, 1, 0, d_sk, pl, true, d_field)) return 1;
+    pl->d_phik_owned    = std::move(d_field);
+    pl->d_lpt2_sk_owned = std::move(d_sk);
+    *out                = pl.release();
     return 0;
 }
 

@@ -30,6 +30,8 @@ int generate_impl(const zd_params *p_in, const zd_pk *pk, const double *eig, int
     size_t free_b = 0, total_b = 0;
     HIPCHECK(hipMemGetInfo(&free_b, &total_b));
     if (p.q2LPT && p.lpt2_dealias && !lpt2_round_fits(&p, (int64_t) free_b - ((int64_t) 16 << 30))) return 1;
+    const bool field2 = fs && fs->order == 2;  // second order on the field: D(k) stays resident beside the round and beside S(k)
+    if (field2 && !field_lpt2_fits(&p, (int64_t) free_b - ((int64_t) 16 << 30))) return 1;
     if (p.stream_factor <= 0) {
         // leave 16 GB for tables, the folded-input slabs (~3 GB), the record ring (8 GB) and the runtime
         int64_t budget = (int64_t) free_b - ((int64_t) 16 << 30);
@@ -58,17 +60,25 @@ int generate_impl(const zd_params *p_in, const zd_pk *pk, const double *eig, int
             p.stream_factor = R2;
         }
     }
+    // ---- second order on a caller-supplied field (zd_kernels_lpt2_field.hip): the intake first, the round reads its D(k) ----
+    DevBuf<cplx> d_field;
+    if (field2 && make_field_phik(&p, pk, *fs, d_field)) return 1;
     // ---- ZD_q2LPT: the second-order round (zd_kernels_lpt2.hip); the chooser has counted S(k) beside the passes' stores ----
-    if (p.q2LPT && make_lpt2_source(&p, pk, d_phik)) return 1;
+    if (p.q2LPT && make_lpt2_source(&p, pk, d_phik, d_field)) return 1;
     // ---- ZD_q3LPT: the third-order round (zd_kernels_lpt3.hip); P3(k) and C_x,y,z(k) stay beside S(k), counted likewise ----
     DevBuf<cplx> d_lpt3[4];
     if (p.q3LPT && make_lpt3_sources(&p, pk, d_phik, d_lpt3)) return 1;
     // ---- a caller-supplied field (zd_kernels_field.hip): PhiK = its modes; no draw is made ----
-    if (fs && make_field_phik(&p, pk, *fs, d_phik)) return 1;
+    if (fs && !field2 && make_field_phik(&p, pk, *fs, d_phik)) return 1;
     PlanPtr plan;
-    if (plan_create_ex(&p, pk, eig, eig_ppd, 0, 1, 0, d_phik, plan, fs != nullptr)) return 1;
+    if (plan_create_ex(&p, pk, eig, eig_ppd, 0, 1, 0, d_phik, plan, fs != nullptr, d_field)) return 1;
     zd_plan *pl      = plan.get();
-    pl->d_phik_owned = std::move(d_phik);
+    if (field2) {  // the plan owns D(k) where PhiK goes, and S(k)
+        pl->d_lpt2_sk_owned = std::move(d_phik);
+        pl->d_phik_owned    = std::move(d_field);
+    } else {
+        pl->d_phik_owned = std::move(d_phik);
+    }
     if (p.q3LPT) adopt_lpt3(pl, d_lpt3);
     const int R = pl->R, recsize = pl->ec.recsize, npass = pl->npass, pstep = pl->pstep;
     const int64_t Pp = zd_plan_local_planes(pl);  // planes delivered per pass

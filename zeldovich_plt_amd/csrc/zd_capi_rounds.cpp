@@ -76,9 +76,15 @@ int lpt2_round_fits(const zd_params *p, int64_t free_bytes) {
 // the x transform; the y columns |kx| < N/2 follow in place, and the z lines of the columns |kx| < N/2, 0 <= ky < N/2 go, truncated
 // to |kz| < N/2 and conjugated (three inverse transforms of a real field are the conjugate of its forward transform), straight
 // into S(k)[ky][kz][x] of the N layout.
-int make_lpt2_source(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d_sk) {
+// field_d != NULL: D(k) of a caller-supplied field (PhiK's layout, resident beside the round); the gradient passes read it where they
+// would draw (zd_kernels_lpt2_field.hip).  Not with the de-aliased round.
+int make_lpt2_source(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d_sk, const cplx *field_d) {
     const bool dq   = p->lpt2_dealias != 0;
     const int64_t N = p->ppd, M = dq ? zd::lpt2_dealias_lattice(N) : N;  // points per side of the round's lattice
+    if (dq && field_d) {
+        fprintf(stderr, "zeldovich_hip: ZD_Field is not supported together with ZD_2LPT_dealias (the de-aliased round draws its modes)\n");
+        return 1;
+    }
     size_t free_b = 0, total_b = 0;
     if (dq && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || !lpt2_round_fits(p, (int64_t) free_b))) return 1;
     zd_params pp     = *p;
@@ -93,7 +99,7 @@ int make_lpt2_source(const zd_params *p, const zd_pk *pk, DevBuf<cplx> &d_sk) {
         pp.lpt2_dealias = 0;
     }
     PlanPtr plan;
-    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 2, nullptr, plan)) return 1;
+    if (plan_create_ex(&pp, pk, nullptr, 0, 0, 1, 2, nullptr, plan, field_d != nullptr, field_d)) return 1;
     zd_plan *ph = plan.get();
     if (dq && (!ph->twr || ph->N != M || ph->g.kmax != zd::kmax((int) (N / 2), p->k_cutoff))) {
         fprintf(stderr, "zeldovich_hip: ZD_2LPT_dealias: the plan on the %lld lattice does not carry the modes of PPD %lld\n", (long long) M,

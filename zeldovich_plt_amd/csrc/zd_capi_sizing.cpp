@@ -111,6 +111,9 @@ int64_t lpt2_round_bytes(const zd_params *p) {
     const int64_t M = p->lpt2_dealias ? zd::lpt2_dealias_lattice(p->ppd) : p->ppd;
     return M * M * (M + store_row_pad(M)) * 16 + M * M * M * 8;
 }
+// second order on a caller-supplied field: D(k) (PhiK, 8 N^3 bytes) stays resident through the round — about 32 N^3 bytes at the peak —
+// and beside S(k) afterwards (16 N^3 bytes beside every pass's store)
+int64_t field_lpt2_round_bytes(const zd_params *p) { return lpt2_round_bytes(p) + fnl_phik_bytes(p->ppd); }
 // ZD_q3LPT memory: P3(k) and C_x,y,z(k) stay beside S(k), 40 N^3 bytes in all; the third-order round before them peaks at its one-array
 // store + the twelve real Hessian fields + S(k) = 120 N^3 bytes (+ the row pad), of which the four new spectra then take 32 N^3
 int64_t lpt3_round_bytes(int64_t N) { return N * N * (N + store_row_pad(N)) * 16 + 12 * N * N * N * 8 + lpt2_sk_bytes(N); }

@@ -2585,6 +2585,7 @@ int launch_gen(const GenConst &g, const GenJumps &J, const JobList &jobs, const 
                int residue, int residue2, const void *twN, void *Y, unsigned *tile_ctr, int max_wgs, hipStream_t st) {
     if (gen_zr(L) == 0) return 2;
     if (g.lpt3) return launch_gen_lpt3(g, J, jobs, S, ky0, nky, L, residue, twN, Y, st);  // third-order plans: zd_kernels_lpt3.hip
+    if (g.lpt2 && g.phik) return launch_gen_lpt2_field(g, jobs, S, ky0, nky, L, residue, twN, Y, st);  // ... on a field: zd_kernels_lpt2_field.hip
     if (g.lpt2) return launch_gen_lpt2(g, J, jobs, S, ky0, nky, L, residue, twN, Y, st);  // second-order plans: zd_kernels_lpt2.hip
 #ifdef ZD_TUNING
     static const bool force_general = getenv("ZD_GEN_GENERAL") != nullptr;

@@ -359,10 +359,11 @@ const char *lpt_bins_refusal(const zd_params &p, int32_t bin_width, int64_t nbin
     return nullptr;
 }
 
-// an LPT plan as zd_plan_create leaves it: the final pass's GenConst with the spectra resident
+// an LPT plan as zd_plan_create leaves it: the final pass's GenConst with the spectra resident (PhiK beside them only as the modes of a
+// caller-supplied field, zd_plan_create_field_lpt: the sweeps then read D there instead of drawing it)
 bool lpt_plan_ready(const zd_plan *pl) {
     const GenConst &g = pl->g;
-    if (!g.lpt2_sk || g.phik || g.gen_phi || g.v1dev || g.qPLT || !pl->d_twN || pl->nranks != 1) return false;
+    if (!g.lpt2_sk || (g.phik && !pl->field) || g.gen_phi || g.v1dev || g.qPLT || !pl->d_twN || pl->nranks != 1) return false;
     return !pl->p.q3LPT || (g.lpt3_p3 && g.lpt3_c[0] && g.lpt3_c[1] && g.lpt3_c[2]);
 }
 
@@ -492,7 +493,7 @@ extern "C" int zd_plan_lpt_power(zd_plan *pl, int32_t bin_width, int64_t nbins, 
     const SweepJumps J = zdsweep::make_sweep_jumps(pl->N);
     const double f2 = zd::lpt2_f2(&p), f3 = zd::lpt3_f3(&p);
     const int nrows = pl->half;
-    const bool fast = g.genf_tab && !g.qonemode;
+    const bool fast = g.genf_tab && !g.qonemode && !g.phik;  // (the table arithmetic draws; a field's modes are read by the general form)
     int rc;
     if (fast) {  // the plane ky = 0 through the general form, every other row through the table arithmetic
         rc = launch_pk_lpt<false>(g, J, 0, 1, pl->S.lG, bin_width, (int) nbins, f2, f3, gcount, gsum, st);

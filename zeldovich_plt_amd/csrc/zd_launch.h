@@ -159,6 +159,11 @@ int launch_gen_lpt2(const GenConst &g, const GenJumps &J, const JobList &jobs, c
 // x lines of the planes [0, nplanes) of a one-array store in gradient pass `pass` (1 .. 4): inverse transform, the pass's term of
 // the source into acc[z][y][x] (N^3 doubles); pass 4 goes on to acc / N^3 and the forward x transform, in place
 int launch_lpt2_xsrc(const StoreLayout &S, int pass, const void *tw, void *data, double *acc, int nplanes, hipStream_t st);
+// ---- second order on a caller-supplied field (zd_kernels_lpt2_field.hip) ----
+// the generator of a second-order plan that carries field modes (GenConst::lpt2 != 0 and GenConst::phik = D(k); launch_gen hands such
+// plans over): launch_gen_lpt2's jobs with D loaded from phik instead of drawn
+int launch_gen_lpt2_field(const GenConst &g, const JobList &jobs, const StoreLayout &S, int ky0, int nky, int L, int residue, const void *twN,
+                          void *Y, hipStream_t st);
 // ---- the de-aliased second-order round on the lattice of m = 3 n / 2 points per side (zd_kernels_lpt2q.hip); tw as for launch_refq_* ----
 // x lines l < nlines at data[l * pitch] in gradient pass `pass` (1 .. 4): launch_lpt2_xsrc's contract with acc[l * m + x] (m^3 doubles)
 int launch_lpt2q_xsrc(int m, const void *tw, int pass, void *data, long long pitch, long long nlines, double *acc, hipStream_t st);

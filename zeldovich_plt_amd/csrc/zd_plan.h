@@ -90,6 +90,9 @@ struct zd_plan {
     zdown::DevBuf<int> d_v1err;
     zdown::DevBuf<zdfft::cplx> d_phik_owned;  // ZD_f_NL: PhiK of the phi round; ZD_q2LPT: the source S(k) — whoever ran the round hands it over
     bool field = false;  // PhiK is a caller-supplied field (zd_plan_create_field): D = PhiK itself, d_fnlM a table of ones
+    // second order on such a field (zd_plan_create_field_lpt, order 2): d_phik_owned holds D(k) (GenConst::phik) and this the source
+    // S(k) (GenConst::lpt2_sk)
+    zdown::DevBuf<zdfft::cplx> d_lpt2_sk_owned;
     zdown::DevBuf<zdfft::cplx> d_lpt3_owned[4];  // ZD_q3LPT: P3(k), C_x(k), C_y(k), C_z(k) of the third-order round, handed over likewise
     // any even PPD (zd_kernels_any.hip): Bluestein tables for the lengths L (z lines) and N (y, x lines)
     bool any = false;  // family >= FAM_REF_COMPOSITE: the reference's arrays as a [plane][array][y][x] store

@@ -469,10 +469,11 @@ static int glass_run(const GlassKeys &gk, const zd_params &p, const zd_param_str
 // ZD_Field_filename, ZD_Field_kind (optional, not in the reference): the modes of the run come from a field instead of ZD_Seed
 // (zd_generate_field); read with zd_param_file_string.  The file is a raw little-endian array [z][y][x]: 4 PPD^3 bytes = float32 (the
 // layout of the density file a ZD_qdensity = 1 run writes), 8 PPD^3 bytes = float64.  It is mapped, not read: the library uploads it in
-// chunks of planes.
+// chunks of planes.  ZD_Field_order (default 1; read only with ZD_Field_filename): 2 = second order on the field (zd_generate_field_lpt);
+// ZD_q2LPT beside ZD_Field_filename keeps its refusal.
 struct FieldKeys {
     char filename[1024] = "";
-    int32_t kind = ZD_FIELD_DENSITY, dtype = ZD_FIELD_F32;
+    int32_t kind = ZD_FIELD_DENSITY, dtype = ZD_FIELD_F32, order = 1;
     const void *data = nullptr;
 };
 static int read_field_keys(const char *path, FieldKeys &k) {
@@ -491,6 +492,17 @@ static int read_field_keys(const char *path, FieldKeys &k) {
         return 1;
     }
     k.kind = !strcmp(kind, "white") ? ZD_FIELD_WHITE : ZD_FIELD_DENSITY;
+    char order[1024];
+    if (zd_param_file_string(path, "ZD_Field_order", order, sizeof(order))) return 1;
+    if (order[0]) {
+        char *end = nullptr;
+        const long n = strtol(order, &end, 10);
+        if (*end || n < INT32_MIN || n > INT32_MAX) {
+            fprintf(stderr, "zeldovich_hip: ZD_Field_order = %s must be an integer (1: Zel'dovich, 2: second order)\n", order);
+            return 1;
+        }
+        k.order = (int32_t) n;  // (the library says which orders it runs)
+    }
     return 0;
 }
 // the file against PPD, mapped; non-zero (one line) if it cannot be read or has neither size
@@ -560,8 +572,10 @@ int main(int argc, char *argv[]) {
             exit(1);
         }
         if (map_field(fk, p.ppd)) exit(1);
-        fprintf(stderr, "field: %s, %s, PPD %lld\n", fk.kind == ZD_FIELD_WHITE ? "white" : "density", fk.dtype == ZD_FIELD_F64 ? "float64" : "float32",
+        fprintf(stderr, "field: %s, %s, PPD %lld", fk.kind == ZD_FIELD_WHITE ? "white" : "density", fk.dtype == ZD_FIELD_F64 ? "float64" : "float32",
                 (long long) p.ppd);
+        if (fk.order != 1) fprintf(stderr, ", order %d", (int) fk.order);
+        fprintf(stderr, "\n");
     }
     const int narray   = p.qdensity == 2 ? 1 : (p.qPLT ? 4 : 2);  // zeldovich.cpp:871-876
     const double memory = cube(p.ppd / 1024.0) * narray * 16.0;
@@ -624,8 +638,9 @@ int main(int argc, char *argv[]) {
 
     zd_stats st;
     memset(&st, 0, sizeof(st));
-    if (fk.filename[0] ? zd_generate_field(&p, &pk, eig, eig_ppd, fk.kind, fk.dtype, fk.data, 0, Writer::callback, &w, &st)
-                       : zd_generate(&p, &pk, eig, eig_ppd, Writer::callback, &w, &st)) {
+    if (fk.filename[0] && fk.order != 1 ? zd_generate_field_lpt(&p, &pk, fk.kind, fk.dtype, fk.data, 0, fk.order, Writer::callback, &w, &st)
+        : fk.filename[0]                ? zd_generate_field(&p, &pk, eig, eig_ppd, fk.kind, fk.dtype, fk.data, 0, Writer::callback, &w, &st)
+                                        : zd_generate(&p, &pk, eig, eig_ppd, Writer::callback, &w, &st)) {
         fprintf(stderr, "zeldovich: generation failed\n");
         exit(1);
     }
